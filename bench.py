@@ -9,10 +9,16 @@ resident kernel re-issued directly, or the T step launches).  Inputs are
 resident in HBM before the timed region.  value = iterations/s summed over all
 ranks = N * T * steps / max-over-ranks wall time.
 
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps of
+the headline config and prints the result line; `--dump-outputs DIR` also writes what
+the last timed step returned to DIR/<name>.npy (dump_outputs).  Everything below that
+takes runs of its own (the dominant kernel's timing and roofline, the "configs",
+backward, gru_section, head_epilogue and cpu_baseline objects) runs only with `--full`.
+
 Workloads (BASELINE.json configs):
   headline (--config, default nyu) = C2: NYUv2 228x304, K=8, T=18, B=8, fp32,
       learned offsets (DCN path), TGASS — the configuration `value` is quoted on;
-  "configs" object (same timing, roofline and PMC fields, per rank):
+  "configs" object (--full; same timing, roofline and PMC fields, per rank):
       C3 kitti    KITTI-DC 240x1216, K=8, T=18, B=4 fp32 (at N=8: C4, B=32 global),
       C5 nyu_k16  NYUv2, K=16 (1x17), T=36, B=16, fp16 storage,
       C1 nyu_b1   NYUv2 B=1 (the CPU config's workload, on the GPU).
@@ -23,7 +29,7 @@ runs its own batch shard (weak scaling, no collective on the data path; SURVEY
 §8e); the process group only carries the max-over-ranks timing and the per-rank
 spread.  `--dry-run` runs the launcher and sharding logic on CPU (gloo, no GPU).
 
-roofline (the dominant kernel: the resident kernel — iterations 2..T, one launch per
+roofline (--full; the dominant kernel: the resident kernel — iterations 2..T, one launch per
 image group (C2: one group of 8 images; C3: two of 2) — where it applies, else the
 per-iteration step kernel):
   achieved = COMPULSORY bytes per launch / its mean duration from dispatch-recorded
@@ -40,7 +46,7 @@ per-iteration step kernel):
       written) / ms_per_step.
   traffic  = HBM-side bytes per launch from profiles/pmc_<config>.json (rocprofv3
       FETCH_SIZE x2 + WRITE_SIZE, separate --pmc passes), or null.
-Extra objects (headline config only, not part of `value`): backward (fp32
+Extra objects (--full; headline config only, not part of `value`): backward (fp32
 forward+backward through autograd), gru_section (the reference's default GRU mode),
 head_epilogue (the decoder's last three convs fused into one HIP kernel vs torch.cat + MIOpen),
 cpu_baseline (rank 0, N=1; the C oracle for the offset path and the reference's
@@ -78,6 +84,8 @@ CONFIGS = {
                    B=1, H=228, W=304, kernel=(3, 3), T=18, dtype="f32", max_depth=10.0, density=500 / (228 * 304)),
 }
 EXTRA = ("kitti", "nyu_k16", "nyu_b1")
+DUMP_MAX_ELEMS = 2 * 1024 * 1024  # --dump-outputs: larger arrays are sampled down to this many elements
+DUMP_SEED = 7240
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 RESIDENT_FIRST = 0x100  # nlspn_time_propagate *resident bit: iteration 1 inside the resident launches
 
@@ -105,6 +113,13 @@ def parse(argv=None):
     ap.add_argument("--no-extra-configs", action="store_true")
     ap.add_argument("--backward-steps", type=int, default=20)
     ap.add_argument("--dry-run", action="store_true", help="launcher + sharding only, on CPU (gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: the dominant kernel's timing and roofline, "
+                         "backward, gru_section, head_epilogue, the extra configs and the CPU baseline (each can "
+                         "still be switched off with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline config's outputs of the last timed step to "
+                         "DIR/<name>.npy (float32; arrays above DUMP_MAX_ELEMS as a fixed seeded sample)")
     return ap.parse_args(argv)
 
 
@@ -223,9 +238,32 @@ def roofline(name, cfg, resident, first_ms, rest_ms, ms_per_step):
     }
 
 
-def measure(name, steps, warmup, kernel_reps, world, rank, dev):
+def dump_outputs(result, out_dir, world, rank):
+    """Write what the last timed replay returned (pred, pred_inter as one (T, B, 1, H, W)
+    array, offset, aff, confidence) to out_dir/<name>.npy as float32 (rank r > 0 of a
+    multi-GPU run: <name>.rank<r>.npy).  An array of more than DUMP_MAX_ELEMS elements is
+    stored as the 1-D sample of its flattened elements at DUMP_MAX_ELEMS indices drawn
+    once, sorted, from numpy's default_rng(DUMP_SEED) for that size, so two builds run
+    with the same arguments store the same elements (at most 5 x 8 MB in all)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"pred": result["pred"], "pred_inter": result["pred_inter_tensor"], "offset": result["offset"],
+              "aff": result["aff"], "confidence": result["confidence"]}
+    for key, t in arrays.items():
+        if t is None:
+            continue
+        x = t.detach().to("cpu", torch.float32).numpy()
+        if x.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(x.size, DUMP_MAX_ELEMS, replace=False))
+            x = x.reshape(-1)[idx]
+        suffix = ".npy" if rank == 0 else f".rank{rank}.npy"
+        np.save(os.path.join(out_dir, key + suffix), np.ascontiguousarray(x))
+
+
+def measure(name, steps, warmup, kernel_reps, world, rank, dev, dump_dir=None):
     """Time one workload on every rank (barrier + synchronize on both sides, max over
-    ranks) and its dominant kernel; returns (result dict, inputs, synthetic arrays)."""
+    ranks) and, with kernel_reps > 0, its dominant kernel (runs of their own, for the
+    roofline); returns (result dict, inputs, synthetic arrays)."""
     from nlspn_eccv20_amd.propagation import PropagationPlan
     cfg = CONFIGS[name]
     inputs, s = make_inputs(cfg, rank, dev)
@@ -240,8 +278,9 @@ def measure(name, steps, warmup, kernel_reps, world, rank, dev):
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     ev0.record()
+    last = None
     for _ in range(steps):
-        plan.replay()
+        last = plan.replay()
     ev1.record()
     torch.cuda.synchronize()
     if world > 1:
@@ -250,8 +289,11 @@ def measure(name, steps, warmup, kernel_reps, world, rank, dev):
     plan.check()  # a resident launch that aborted raises here (never silent)
     spread = gather_over_ranks(mine, dev)
     elapsed = max_over_ranks(mine, dev)
-    first_ms, rest_ms, resident = kernel_time(plan, inputs, cfg, kernel_reps, dev)
-    plan.check()
+    if dump_dir and last is not None:
+        dump_outputs(last, dump_dir, world, rank)
+    if kernel_reps > 0:
+        first_ms, rest_ms, resident = kernel_time(plan, inputs, cfg, kernel_reps, dev)
+        plan.check()
     plan.close()
     ms_per_step = 1e3 * elapsed / steps
     out = {
@@ -262,8 +304,9 @@ def measure(name, steps, warmup, kernel_reps, world, rank, dev):
         "shard": list(shard_range(cfg["B"] * world, world, rank)),
         "gpu_event_ms_per_step": round(ev0.elapsed_time(ev1) / steps, 4),
         "rank_ms_per_step": [round(1e3 * x / steps, 4) for x in spread],
-        "roofline": roofline(name, cfg, resident, first_ms, rest_ms, ms_per_step),
     }
+    if kernel_reps > 0:
+        out["roofline"] = roofline(name, cfg, resident, first_ms, rest_ms, ms_per_step)
     return out, inputs, s
 
 
@@ -600,7 +643,9 @@ def main():
     torch.cuda.set_device(dev)
     cfg = CONFIGS[a.config]
 
-    head, inputs, _ = measure(a.config, a.steps, a.warmup, a.kernel_reps, world, rank, dev)
+    # a plain run measures the headline figure alone; every other leg runs under --full
+    head, inputs, _ = measure(a.config, a.steps, a.warmup, max(1, a.kernel_reps) if a.full else 0, world, rank, dev,
+                              dump_dir=a.dump_outputs)
     out = {
         "metric": baseline_metric(),
         "value": head["value"], "unit": "iters/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -611,27 +656,28 @@ def main():
                    "H": cfg["H"], "W": cfg["W"], "K": cfg["kernel"][0] * cfg["kernel"][1] - 1,
                    "kernel": list(cfg["kernel"]), "prop_time": cfg["T"],
                    "parallelism": f"dp{world} (batch shards, no collective)"},
-        "roofline": head["roofline"],
         "gpu_event_ms_per_step": head["gpu_event_ms_per_step"],
         "rank_ms_per_step": head["rank_ms_per_step"],
     }
-    if cfg["dtype"] == "f32" and not a.no_backward:
+    if a.full:
+        out["roofline"] = head["roofline"]
+    if a.full and cfg["dtype"] == "f32" and not a.no_backward:
         out["backward"] = backward_timing(inputs, cfg, a.backward_steps)
-    if cfg["dtype"] == "f32" and cfg["kernel"] == (3, 3) and not a.no_gru:
+    if a.full and cfg["dtype"] == "f32" and cfg["kernel"] == (3, 3) and not a.no_gru:
         out["gru_section"] = gru_section_timing(inputs, cfg, a.backward_steps, dev)
     del inputs
-    if cfg["dtype"] == "f32" and not a.no_heads:
+    if a.full and cfg["dtype"] == "f32" and not a.no_heads:
         out["head_epilogue"] = head_epilogue_timing(cfg, dev)
         torch.cuda.empty_cache()
-    if not a.no_extra_configs:
+    if a.full and not a.no_extra_configs:
         out["configs"] = {}
         for name in EXTRA:
             if name == a.config:
                 continue
-            r, _, _ = measure(name, a.steps, a.warmup, a.kernel_reps, world, rank, dev)
+            r, _, _ = measure(name, a.steps, a.warmup, max(1, a.kernel_reps), world, rank, dev)
             out["configs"][CONFIGS[name]["id"]] = r
             torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.cpu_reps)
     if rank == 0:
         print(json.dumps(out), flush=True)

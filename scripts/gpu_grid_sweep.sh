@@ -5,7 +5,7 @@ set -o pipefail
 O=gpurun_out/grid; mkdir -p $O
 run() {  # config grid
   ( [ "$2" != "-" ] && export NLSPN_RES_GRID=$2
-    timeout -k 10 120 python bench.py --config $1 --no-cpu-baseline --no-backward --no-gru --no-extra-configs \
+    timeout -k 10 120 python bench.py --full --config $1 --no-cpu-baseline --no-backward --no-gru --no-extra-configs \
         --steps 200 --warmup 20 > $O/$1_$2.json 2> $O/$1_$2.err ) || exit 1
   python -c "import json;d=json.load(open('$O/$1_$2.json'));print('$1', '$2', d['value'], d['ms_per_step'], d['roofline']['kernel_ms_mean'])"
 }

@@ -15,7 +15,7 @@ for CFG in "$@"; do
            "dram:TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_DRAM_sum"; do
     tag=${P%%:*}; C=${P#*:}
     timeout -s KILL 120 rocprofv3 --pmc $C --kernel-trace -d $O/${CFG}_$tag -o run --output-format csv -- \
-        python3 $R/bench.py --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-backward --no-gru \
+        python3 $R/bench.py --full --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-backward --no-gru \
         --no-extra-configs --no-heads --kernel-reps 5 > $O/${CFG}_$tag.log 2>&1 || { tail -20 $O/${CFG}_$tag.log; exit 1; }
   done
 done

@@ -15,7 +15,7 @@ if [ "${AB_ENV:-NLSPN_RES_FIRST=0}" != "none" ]; then
   cat $O/ab.json
 fi
 if [ -z "$NOBENCH" ]; then
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-backward --no-gru --no-heads > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-backward --no-gru --no-heads > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
   python -c "import json;d=json.load(open('$O/bench.json'));print('C2',d['value'],d['roofline']['kernel_ms_mean'],{k:(v['value'],v['roofline']['kernel_ms_mean']) for k,v in d['configs'].items()})"
 fi
 for CFG in ${TRACE:-nyu}; do

@@ -25,11 +25,11 @@ if [ "${ABSTEP1:-0}" = 1 ]; then
       --configs nyu_k16 > $O/ab_step1_px2.json 2> $O/ab_step1_px2.err || { tail -5 $O/ab_step1_px2.err; exit 1; }
   cat $O/ab_step1_px2.json
 fi
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 --no-extra-configs --no-cpu-baseline --no-heads --no-gru \
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --no-extra-configs --no-cpu-baseline --no-heads --no-gru \
     > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python -c "import json;d=json.load(open('$O/bench.json'));print(d['value'], json.dumps(d['backward']))"
 if [ "${BWDPROF:-0}" = 1 ]; then
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o bwd --output-format csv -- \
-      python3 $R/bench.py --steps 10 --warmup 3 --no-extra-configs --no-cpu-baseline --no-heads --no-gru > $O/prof.log 2>&1 || exit 1
+      python3 $R/bench.py --full --steps 10 --warmup 3 --no-extra-configs --no-cpu-baseline --no-heads --no-gru > $O/prof.log 2>&1 || exit 1
 fi

@@ -20,6 +20,6 @@ if [ "${SMOKE:-0}" = 1 ]; then
   tail -1 $O/smoke.log
 fi
 if [ "${BENCH:-0}" = 1 ]; then
-  timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
   python -c "import json;d=json.load(open('$O/bench.json'));print(d['value'], d['ms_per_step'], {k: v['value'] for k, v in d.get('configs', {}).items()})"
 fi

@@ -5,7 +5,7 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r6_gru_${1:-a}; mkdir -p $O
 cd $R
-timeout -k 10 400 python bench.py --steps 5 --warmup 2 --no-backward --no-heads --no-extra-configs --no-cpu-baseline \
+timeout -k 10 400 python bench.py --full --steps 5 --warmup 2 --no-backward --no-heads --no-extra-configs --no-cpu-baseline \
     > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python -c "import json;d=json.load(open('$O/bench.json'));print(json.dumps(d['gru_section']))"
 cd /tmp && export TMPDIR=/tmp

@@ -10,6 +10,6 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_gru.py -m gpu -x -q -p no:c
 rc=$?; tail -2 $O/pytest.log; [ $rc -ne 0 ] && exit $rc
 timeout -k 10 300 python tools/gc_bench.py > $O/gc_bench.json 2> $O/gc_bench.err || { tail -5 $O/gc_bench.err; exit 1; }
 cat $O/gc_bench.json
-timeout -k 10 400 python bench.py --steps 5 --warmup 2 --no-backward --no-heads --no-extra-configs --no-cpu-baseline \
+timeout -k 10 400 python bench.py --full --steps 5 --warmup 2 --no-backward --no-heads --no-extra-configs --no-cpu-baseline \
     > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python -c "import json;d=json.load(open('$O/bench.json'));print(json.dumps(d['gru_section']))"

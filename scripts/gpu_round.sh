@@ -16,17 +16,17 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --t
     > $O/pytest_gpu.log 2>&1
 rc=$?; echo "pytest rc=$rc" >> $O/pytest_gpu.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || exit 1
-NLSPN_RESIDENT=0 timeout -k 10 300 python bench.py --no-backward --no-gru --no-extra-configs --no-cpu-baseline \
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
+NLSPN_RESIDENT=0 timeout -k 10 300 python bench.py --full --no-backward --no-gru --no-extra-configs --no-cpu-baseline \
     > $O/bench_nyu_steps.json 2> $O/bench_nyu_steps.err || exit 1
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats -o bench --output-format csv -- \
-    python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-backward --no-gru > $O/stats.log 2>&1 || exit 1
+    python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-backward --no-gru > $O/stats.log 2>&1 || exit 1
 # kernel stats per config (kernels are shared between configs, so the default run's
 # averages mix them): each bench config alone, for the roofline cross-check
 for CFG in nyu kitti nyu_k16 nyu_b1; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats_$CFG -o bench --output-format csv -- \
-      python3 $R/bench.py --config $CFG --steps 20 --warmup 5 --no-cpu-baseline --no-backward --no-gru --no-heads \
+      python3 $R/bench.py --full --config $CFG --steps 20 --warmup 5 --no-cpu-baseline --no-backward --no-gru --no-heads \
       --no-extra-configs > $O/stats_$CFG.log 2>&1 || exit 1
 done
 fi
@@ -36,7 +36,7 @@ cd /tmp && export TMPDIR=/tmp
 for CFG in nyu kitti nyu_k16 nyu_b1; do
   for C in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 300 rocprofv3 --pmc $C --kernel-trace -d $O/pmc_${CFG}_$C -o run --output-format csv -- \
-        python3 $R/bench.py --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-backward --no-gru \
+        python3 $R/bench.py --full --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-backward --no-gru \
         --no-extra-configs --no-heads --kernel-reps 5 > $O/pmc_${CFG}_$C.log 2>&1 || exit 1
   done
   python3 $R/tools/pmc_summary.py --bench $CFG "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes over bench.py --config $CFG (scripts/gpu_round.sh $TAG)" \

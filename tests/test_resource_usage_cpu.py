@@ -53,12 +53,12 @@ def _scratch_cap(name):
 _FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize"]
 
 
-def _rows():
+def _rows(tmp):
     rows = RU.load_build()
     if any("prop_resident_kernel" in n for n in rows):
         return rows
     out = subprocess.run(["/opt/rocm/bin/hipcc", *_FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", "-o",
-                          "/tmp/nlspn_ru_test.o", os.path.join(CSRC, "nlspn_kern_resident.hip")],
+                          os.path.join(tmp, "nlspn_ru_test.o"), os.path.join(CSRC, "nlspn_kern_resident.hip")],
                          capture_output=True, text=True, cwd=CSRC)
     assert out.returncode == 0, out.stderr[-2000:]
     return RU.parse(out.stderr)
@@ -76,24 +76,24 @@ def test_hot_kernels_have_no_scratch():
     assert not vspill, f"VGPR spills in hot kernels: {vspill}"
 
 
-def test_resident_kernel_registers_and_scratch():
+def test_resident_kernel_registers_and_scratch(tmp_path):
     """The resident kernel's launch bound (768 threads = 3 waves per SIMD) caps it at
     168 VGPRs; its scratch stays under the cap, and its iteration loop (nested in the
     image-group loop) holds at most RESIDENT_LOOP_RELOADS scratch instructions (device
     assembly)."""
-    rows = _rows()
+    rows = _rows(str(tmp_path))
     res = {n: r for n, r in rows.items() if "prop_resident_kernel" in n}
     assert res and all(r["VGPRs"] <= 168 and r.get("Occupancy", 0) >= 3 for n, r in res.items()), res
     assert any("ELi576E" in n for n in res) and any("ELi128E" in n for n in res), "fixed thread-count builds missing"
     assert any(_groups(n) for n in res) and any(not _groups(n) for n in res), "GROUPS builds missing"
     over = {n: r.get("ScratchSize", 0) for n, r in res.items() if r.get("ScratchSize", 0) > _scratch_cap(n)}
     assert not over, over
-    asm = ""
+    asm, asm_path = "", str(tmp_path / "nlspn_res_test.s")
     for tu in ("nlspn_kern_resident.hip", "nlspn_kern_resident_wide.hip"):  # 3x3; 1x17 and 5x5
-        out = subprocess.run(["/opt/rocm/bin/hipcc", *_FLAGS, "--cuda-device-only", "-S", "-o", "/tmp/nlspn_res_test.s",
+        out = subprocess.run(["/opt/rocm/bin/hipcc", *_FLAGS, "--cuda-device-only", "-S", "-o", asm_path,
                               os.path.join(CSRC, tu)], capture_output=True, text=True, cwd=CSRC)
         assert out.returncode == 0, out.stderr[-2000:]
-        with open("/tmp/nlspn_res_test.s") as f:
+        with open(asm_path) as f:
             asm += f.read()
     for name in res:
         loop = RU.loop_scratch(asm, name, 2 if _groups(name) else 1)["loop"]
