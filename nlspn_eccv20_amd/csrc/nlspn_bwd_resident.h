@@ -45,17 +45,12 @@
 #pragma once
 
 #include "nlspn_backward.h"
+#include "nlspn_plan.h"  // kBrNT, kBrPX, kBrR, kBrMaxParts, kBrMaxCells, kBrLdsBytes (shared with br_plan)
 
 namespace nlspn {
 
-constexpr int kBrNT = 1024;        // threads per part
-constexpr int kBrPX = 3;           // pixels per thread, at most
-constexpr int kBrR = 8;            // LDS window halo (the step form's RY = RX = 8)
-constexpr int kBrMaxParts = 256;   // parts per launch (one per CU)
 constexpr int kBrMaskWords = kBrMaxParts / 32;
 constexpr int kBrLine = 32;        // words per 128-B line: every counter on a line of its own
-constexpr int kBrMaxCells = 8192;  // LDS window cells (64 KiB of fixed-point sums)
-constexpr int kBrLdsBytes = 150 * 1024;  // dynamic LDS: window (8 B per cell) + affinities (32 B per pixel)
 constexpr unsigned kBrSpinLimit = 1u << 22;
 // sync words: line 0 = {abort, registration count}; line 1 + i = part i's arrival count;
 // then one adjacency row (kBrMaskWords) per part.  Zeroed by the host before each launch.

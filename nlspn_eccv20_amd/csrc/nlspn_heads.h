@@ -403,4 +403,17 @@ static __global__ void heads_pack_kernel(HeadsPackArgs a) {
     }
 }
 
+// The builds of heads_kernel the library has, as X(MB, VEC, ABL, PRO), written once for
+// the unit that instantiates them (NLSPN_HD_INST, nlspn_kern_heads.hip) and the one that
+// launches them (NLSPN_HD_EXTERN, nlspn_seam.hip): the epilogue per output-block count; ABL
+// 1..3 the ablation variants (NLSPN_HEADS_DBG bits 1, 2; tools/head_ablate.py); PRO the fused
+// propagation prologue (nlspn_head_epilogue_prologue).
+#define NLSPN_HD_BUILDS(X)                                                                     \
+    X(1, true, 0, false) X(1, false, 0, false) X(2, true, 0, false) X(2, false, 0, false)      \
+    X(3, true, 0, false) X(3, false, 0, false) X(5, true, 0, false) X(5, false, 0, false)      \
+    X(1, true, 1, false) X(1, true, 2, false) X(1, true, 3, false) X(1, true, 0, true) X(1, false, 0, true)
+#define NLSPN_HD_SPEC(LINKAGE, MB, VEC, ABL, PRO) LINKAGE template __global__ void heads_kernel<MB, VEC, ABL, PRO>(HeadsArgs);
+#define NLSPN_HD_INST(...) NLSPN_HD_SPEC(, __VA_ARGS__)
+#define NLSPN_HD_EXTERN(...) NLSPN_HD_SPEC(extern, __VA_ARGS__)
+
 }  // namespace nlspn

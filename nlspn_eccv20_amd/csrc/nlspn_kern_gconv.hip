@@ -1,5 +1,5 @@
 // Device code of the GRU-mode convolutions (nlspn_gconv.h), their own translation unit.
-// Launched from nlspn_capi.hip (nlspn_gconv); the configurations are NLSPN_GC_CONFIGS.
+// Launched from nlspn_gconv_host.hip (nlspn_gconv); the configurations are NLSPN_GC_CONFIGS.
 #include "nlspn_gconv.h"
 
 namespace nlspn {

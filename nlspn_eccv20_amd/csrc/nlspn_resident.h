@@ -52,7 +52,7 @@
 // Residency: G = B * gy * gx workgroups, at most one per CU (the dynamic LDS
 // request exceeds half a CU's LDS) and G <= CU count, so the whole grid is
 // resident (the host serialises resident launches of one device across streams,
-// nlspn_capi.hip res_guard).  Every spin is bounded: on timeout a part raises the
+// nlspn_host.hip res_guard).  Every spin is bounded: on timeout a part raises the
 // abort word (sync[0]) and the device's host-mapped sticky status word
 // (ResArgs::status, read by nlspn_resident_status without a device sync), and every
 // part that sees the abort fills its own quads of the planes it has not written
@@ -60,6 +60,7 @@
 #pragma once
 
 #include "nlspn_common.h"
+#include "nlspn_plan.h"  // the geometry constants shared with the planner (kResMaxNT, res_px, res_win_cells ...)
 #include "nlspn_step.h"
 
 namespace nlspn {
@@ -121,7 +122,6 @@ struct ResArgs {
 
 typedef const __attribute__((address_space(4))) ResArgs ResArgsK;  // the kernarg segment's ResArgs
 
-constexpr int kResMaxNT = 768;                  // launch bound (threads per part)
 constexpr int kResSMax = 1;                      // staging quads per thread per round
 constexpr int kResPre = 2;                       // the prologue's window staging: quads per thread in flight
 #ifndef NLSPN_RES_SPIN_SLEEP
@@ -131,47 +131,6 @@ constexpr int kResPre = 2;                       // the prologue's window stagin
 #define NLSPN_RES_WTRACE 0  // trace builds: per-wave stamps too (they cost the loop 16 B/lane of scratch)
 #endif
 constexpr bool kResWTrace = NLSPN_RES_WTRACE;
-constexpr int kResRY = 8, kResRXQ = 2;           // fallback window halo (3x3): rows, quad columns
-// the fallback halo of a kh x kw geometry: the 3x3 one plus the taps' wider base reach
-__host__ __device__ constexpr int res_ry(int kh) { return kResRY + (kh > 3 ? (kh - 3) / 2 : 0); }
-__host__ __device__ constexpr int res_rxq(int kw) { return kResRXQ + (kw > 3 ? ((kw - 3) / 2 + 3) / 4 : 0); }
-// pixels per thread of a kh x kw geometry (a quad's 4 pixels as 1, 2 or 4 threads): the tap
-// geometry of K x PX tap-pixels lives in registers (2 per tap-pixel + half a packed index), so
-// PX shrinks as K grows — 3x3 (K = 8): 4; 1x17 (K = 16): 2; 5x5 (K = 24): 1; 0: not resident
-// (7x7, K = 48: 4 x 48 registers of tap geometry alone pass the 168-VGPR cap)
-__host__ __device__ constexpr int res_px(int kh, int kw) {
-    return (kh == 3 && kw == 3) ? 4 : (kh == 1 && kw == 17) ? 2 : (kh == 5 && kw == 5) ? 1 : 0;
-}
-// bytes of a thread's LDS rows: the K affinities, 1 - sum, conf', dep of its PX pixels
-__host__ __device__ constexpr int res_row_bytes(int K, int px) { return (K + 3) * px * 4; }
-constexpr int kResPadX = 4;                      // zero columns either side of the window (keeps 16-B rows)
-// The export list (per-line write-through, below): at most kResNC foreign windows per part
-// (the parts on another XCC whose windows reach this part's 128-B lines), two words each
-constexpr int kResNC = 28;
-constexpr int kResCtl = 8 + 2 * kResNC;          // LDS control words ahead of the window
-constexpr int kResAS = 11;                       // float4 per thread (3x3): K = 8 affinities, 1 - sum, conf', dep
-constexpr int kResLds = 160 * 1024;              // LDS per CU
-
-// LDS cells per copy of the f window for nt threads: what the per-thread rows leave,
-// a multiple of 4 (16-B aligned copies), both copies addressable by 16-bit indices.
-// (A PITCH build's copies stay within 16-bit byte addresses: at most 8,184 cells.)
-__host__ __device__ constexpr int res_win_cells(int nt, int row_bytes = 16 * kResAS, int cap = 32764) {
-    return ((kResLds - 4 * kResCtl - row_bytes * nt) / 8 / 4 * 4) < cap
-               ? ((kResLds - 4 * kResCtl - row_bytes * nt) / 8 / 4 * 4)
-               : cap;
-}
-
-// the compile-time window pitch of a fixed-thread-count build (0: the pitch is the window's
-// width, a run-time value): 128 cells for 576 threads, whose two window copies span
-// 2 * 7,740 cells = 61.9 KB of byte addresses (below 64 KB: 16-bit)
-__host__ __device__ constexpr int res_pitch(int ntc) { return ntc == 576 ? 128 : 0; }
-// the window cells per copy of a build (threads ntc, 0: nt at run time) and geometry
-__host__ __device__ constexpr int res_build_cells(int ntc, int nt, int K, int px) {
-    return res_win_cells(ntc ? ntc : nt, res_row_bytes(K, px), res_pitch(ntc) ? 8184 : 32764);
-}
-static_assert(4 * (kResCtl + 2 * res_win_cells(576)) < 65536, "576-thread window byte addresses need 16 bits");
-static_assert(kResCtl % 4 == 0, "the window starts 16-B aligned");
-
 constexpr unsigned kResSpinLimit = 1u << 22;     // ~seconds of polling before giving up
 #ifndef NLSPN_RES_NOGP
 constexpr bool kResGeneralPath = true;
@@ -182,13 +141,6 @@ constexpr unsigned kSc1 = 16u;                   // buffer-instruction aux bit: 
 constexpr unsigned kResOffInserted = 0x100u;      // ResArgs::flags: offsets in the inserted 2(K+1)-plane layout
 constexpr unsigned kResL2 = 0x400u;               // ResArgs::flags: same-XCD hand-offs may stay in the XCD's L2
 constexpr unsigned kResFirst = 0x800u;            // ResArgs::flags: the prologue and iteration 1 in the launch
-// The sync workspace: one 128-B line per word group — [0] the abort word, [1] the count of
-// parts that have finished, then per part i (blockIdx) the line kResLine * (1 + i) holding
-// (word + 1) its tagged XCC id.  No two parts share a line, so a line is only ever written
-// from one XCD.  The words are zero when a launch starts and zero again when it ends: the
-// last part to finish (the count) clears them (res_finish), so a plan's launches need no
-// clearing pass (the host clears a workspace once, before its first resident launch).
-constexpr int kResLine = 32;
 // "not yet written" values of the handed-off planes (nlspn_step.h kPoison32 / kPoison16,
 // also stored by step 1): signalling NaNs (quiet bit clear), which no arithmetic result is
 // (an instruction returns a NaN quieted), so a computed p_t never equals them
@@ -1425,5 +1377,37 @@ __global__ void __launch_bounds__(MAXNT) prop_resident_kernel(ResArgs a) {
     lds_barrier();  // every wave has made its last read of the sync words
     res_finish(sync);
 }
+
+// The builds of prop_resident_kernel the library has, as X(KH, KW, NTC, GROUPS, FIRST, PXO),
+// written once for the units that instantiate them (NLSPN_RES_INST: nlspn_kern_resident.hip
+// the 3x3 ones, nlspn_kern_resident_wide.hip the others) and the one that launches them
+// (NLSPN_RES_EXTERN and the lookup, nlspn_prop_fwd.hip).
+// 3x3 (the reference default; quads per thread).  NTC: compile-time thread counts of the
+// shapes the bench configs plan (C2 NYU B=8: 576; one NYU image, C1: 128), so the LDS row
+// addresses fold into immediates; 0 = any other shape (thread count read at run time).
+// GROUPS = true: several image groups in turn in one launch (C3 KITTI B=4: 576 threads;
+// others: run-time count, the step-1 form only: its prologue form held scratch reloads in
+// the iteration loop, and the planner keeps step 1 for such merged launches).  FIRST: the
+// forward prologue and iteration 1 inside the launch (ResArgs kResFirst), or after step 1.
+// PXO 2 / 1: the split-quad builds (small 3x3 parts, C1): two threads per quad at 192
+// threads, four at 320.
+#define NLSPN_RES_BUILDS_3X3(X)                                                                     \
+    X(3, 3, 0, false, true, 0) X(3, 3, 576, false, true, 0) X(3, 3, 128, false, true, 0)            \
+    X(3, 3, 576, true, true, 0) X(3, 3, 0, false, false, 0) X(3, 3, 576, false, false, 0)           \
+    X(3, 3, 128, false, false, 0) X(3, 3, 576, true, false, 0) X(3, 3, 0, true, false, 0)           \
+    X(3, 3, 192, false, false, 2) X(3, 3, 320, false, false, 1) X(3, 3, 320, false, true, 1)
+// 1x17 (K = 16, two pixels per thread: the C5 stress config's taps): the 576-thread builds
+// (compile-time pitch; GROUPS for several image groups per launch, the C5 shape: 16 images in
+// 4 groups of 4) and the run-time-thread-count builds; 5x5 (K = 24, a pixel per thread).  The
+// step-1 form only (FIRST = false): a thread's raw-plane loads are 4 B or less, and the
+// prologue's loads from HBM cost C5 more than step 1 does (nlspn_plan.h res_plan_first).
+#define NLSPN_RES_BUILDS_WIDE(X)                                                                    \
+    X(1, 17, 0, false, false, 0) X(1, 17, 576, false, false, 0) X(1, 17, 576, true, false, 0)       \
+    X(1, 17, 0, true, false, 0) X(5, 5, 0, false, false, 0)
+#define NLSPN_RES_SPEC(LINKAGE, KH, KW, NTC, G, F, PXO)                                                                  \
+    LINKAGE template __global__ void prop_resident_kernel<float, KH, KW, kResMaxNT, kResSMax, NTC, G, F, PXO>(ResArgs);  \
+    LINKAGE template __global__ void prop_resident_kernel<__half, KH, KW, kResMaxNT, kResSMax, NTC, G, F, PXO>(ResArgs);
+#define NLSPN_RES_INST(...) NLSPN_RES_SPEC(, __VA_ARGS__)
+#define NLSPN_RES_EXTERN(...) NLSPN_RES_SPEC(extern, __VA_ARGS__)
 
 }  // namespace nlspn

@@ -1,0 +1,264 @@
+// C ABI of the seam-2 and head entry points (see include/nlspn_prop.h): the modulated
+// deformable convolution forward and backward, the S2D pyramid, the head epilogue and its
+// weight packing, and the affinity normalisation's forward.  The DCN, S2D, packing and
+// normalisation kernels are instantiated here; the head kernels in nlspn_kern_heads.hip.
+#include "nlspn_host.h"
+#include "nlspn_affnorm.h"
+#include "nlspn_heads.h"
+#include "nlspn_mdcn.h"
+#include "nlspn_s2d.h"
+
+namespace nlspn {
+NLSPN_HD_BUILDS(NLSPN_HD_EXTERN)  // defined in nlspn_kern_heads.hip
+}  // namespace nlspn
+
+using namespace nlspn;
+
+namespace {
+
+// ------------------------------------------------------- affinity-normalisation dispatch
+template <typename T, int K>
+const void *affnorm_fn(bool vec) {
+    return vec ? reinterpret_cast<const void *>(&affnorm_kernel<T, K, 4>)
+               : reinterpret_cast<const void *>(&affnorm_kernel<T, K, 1>);
+}
+template <typename T>
+const void *select_affnorm(int K, bool vec) {
+    switch (K) {
+        case 8: return affnorm_fn<T, 8>(vec);
+        case 16: return affnorm_fn<T, 16>(vec);
+        case 24: return affnorm_fn<T, 24>(vec);
+        case 48: return affnorm_fn<T, 48>(vec);
+        default: return nullptr;
+    }
+}
+
+// ------------------------------------------------------------------------------ DCN
+// The argument check shared by the DCN forward and backward; sets the output size.
+int check_mdcn(int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+               int group, int deformable_group, int *Ho, int *Wo) {
+    if (B < 1 || C < 1 || H < 1 || W < 1 || Cout < 1 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1 ||
+        group < 1 || deformable_group < 1 || ph < 0 || pw < 0)
+        return fail(NLSPN_EINVAL, "invalid DCN arguments");
+    if ((C % group) != 0 || (Cout % group) != 0)
+        return fail(NLSPN_EINVAL, "channels(%d) and channels_out(%d) must divide group(%d)", C, Cout, group);
+    if ((C % deformable_group) != 0)
+        return fail(NLSPN_EINVAL, "channels(%d) must divide deformable_group(%d)", C, deformable_group);
+    *Ho = (H + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1;
+    *Wo = (W + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
+    if (*Ho < 1 || *Wo < 1) return fail(NLSPN_EINVAL, "output size %dx%d is empty", *Ho, *Wo);
+    return NLSPN_OK;
+}
+
+// The two DCN backward launches (nlspn_mdcn.h) in arithmetic type A (float or double).
+template <typename A>
+int mdcn_backward_impl(const void *input, const void *weight, const void *offset, const void *mask,
+                       const void *grad_output, void *grad_input, void *grad_offset, void *grad_mask, void *grad_weight,
+                       void *grad_bias, int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph,
+                       int pw, int dh, int dw, int group, int dg, int Ho, int Wo, long long nd, long long nw,
+                       hipStream_t s) {
+    MdcnBwdArgs<A> a{static_cast<const A *>(input), static_cast<const A *>(weight), static_cast<const A *>(offset),
+                     static_cast<const A *>(mask), static_cast<const A *>(grad_output), static_cast<A *>(grad_input),
+                     static_cast<A *>(grad_offset), static_cast<A *>(grad_mask), static_cast<A *>(grad_weight),
+                     static_cast<A *>(grad_bias), B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, group, dg, Ho, Wo};
+    NLSPN_HIP_TRY(hipMemsetAsync(grad_input, 0, sizeof(A) * (size_t)B * C * H * W, s));
+    void *args[] = {&a};
+    NLSPN_TRY(launch_kernel(reinterpret_cast<const void *>(&mdcn_bwd_data_kernel<A>), dim3(elementwise_grid(nd)), dim3(256),
+                            args, 0, s, "nlspn_mdcn_backward data"));
+    return launch_kernel(reinterpret_cast<const void *>(&mdcn_bwd_weight_kernel<A>), dim3((unsigned)nw), dim3(256), args,
+                         0, s, "nlspn_mdcn_backward weight");
+}
+
+// ---------------------------------------------------------------------- head epilogue
+int head_mb(int nout) {
+    const int mb = (nout + 2 + 31) / 32;
+    return mb <= 3 ? mb : (mb <= 5 ? 5 : -1);
+}
+
+// Shared launch of both head-epilogue entry points.
+int launch_heads(HeadsArgs &a, void *stream) {
+    const int B = a.B, C = a.C, W = a.W, nout = a.nout;
+    const long long grid = (long long)B * a.tiles_x * a.tiles_y;
+    if (grid > 0x7fffffffLL) return fail(NLSPN_EINVAL, "input too large");
+    const bool vec = W % 4 == 0 && aligned(a.fe1, 16) && aligned(a.fd_oa, 16) && aligned(a.fd_id, 16) &&
+                     aligned(a.fd_cf, 16);
+    const void *fn = nullptr;
+    int lds = 0;
+    switch (head_mb(nout)) {
+#define NLSPN_HD_CASE(MB)                                                                                   \
+    case MB:                                                                                                \
+        fn = vec ? reinterpret_cast<const void *>(&heads_kernel<MB, true>)                                  \
+                 : reinterpret_cast<const void *>(&heads_kernel<MB, false>);                                \
+        lds = (int)sizeof(float) * (HdCfg<MB>::LDS_FLOATS + 2 * C * 9);                                     \
+        break;
+        NLSPN_HD_CASE(1)
+        NLSPN_HD_CASE(2)
+        NLSPN_HD_CASE(3)
+        NLSPN_HD_CASE(5)
+#undef NLSPN_HD_CASE
+        default: return fail(NLSPN_EUNSUPPORTED, "head epilogue: nout=%d", nout);
+    }
+    if (a.aff_out)  // the fused propagation prologue (nout = 24: MB = 1)
+        fn = vec ? reinterpret_cast<const void *>(&heads_kernel<1, true, 0, true>)
+                 : reinterpret_cast<const void *>(&heads_kernel<1, false, 0, true>);
+    else if (kExperiments && vec && head_mb(nout) == 1 && (a.dbg & 3u)) {  // ablation kernels (timing only)
+        const void *abl[3] = {reinterpret_cast<const void *>(&heads_kernel<1, true, 1>),
+                              reinterpret_cast<const void *>(&heads_kernel<1, true, 2>),
+                              reinterpret_cast<const void *>(&heads_kernel<1, true, 3>)};
+        fn = abl[(a.dbg & 3u) - 1];
+    }
+    // The attribute is per device (the current device is the caller's, and DataParallel
+    // replicas launch from their own threads): set_lds_attr makes the driver call once
+    // per device and kernel.
+    if (lds > 65536) NLSPN_TRY(set_lds_attr(fn, lds));
+    void *args[] = {&a};
+    return launch_kernel(fn, dim3((unsigned)grid), dim3(kHdNT), args, (size_t)lds, as_stream(stream), "nlspn_head_epilogue");
+}
+
+}  // namespace
+
+extern "C" {
+
+int nlspn_s2d_pyramid(int dtype, const void *dep, const float *w1, const float *b1, const float *w2,
+                      const float *b2, void *out, void *pyr, int B, int H, int W, void *stream) {
+    NLSPN_TRY(check_f32(dtype, "S2D pyramid"));
+    NLSPN_TRY(check_nonempty(B, H, W));
+    if (!dep || !w1 || !b1 || !w2 || !b2 || !out) return fail(NLSPN_EINVAL, "null required pointer");
+    S2DArgs a{static_cast<const float *>(dep), w1, b1, w2, b2, static_cast<float *>(out), static_cast<float *>(pyr),
+              B, H, W, (W + kS2DTW - 1) / kS2DTW, (H + kS2DTH - 1) / kS2DTH, 0u};
+    a.dbg = env_dbg("NLSPN_S2D_DBG");
+    const long long grid = (long long)B * a.tiles_x * a.tiles_y;
+    if (grid > 0x7fffffffLL) return fail(NLSPN_EINVAL, "input too large");
+    void *args[] = {&a};
+    return launch_kernel(reinterpret_cast<const void *>(&s2d_pyramid_kernel), dim3((unsigned)grid), dim3(256), args, 0,
+                         as_stream(stream), "nlspn_s2d_pyramid");
+}
+
+int nlspn_head_packed_size(int C, int nout, int64_t *wm_floats, int64_t *wv_floats, int64_t *bias_floats) {
+    if (C < 16 || C % 16 || nout < 1) return fail(NLSPN_EINVAL, "head epilogue: C=%d (multiple of 16) nout=%d", C, nout);
+    const int mb = head_mb(nout);
+    if (mb < 0) return fail(NLSPN_EUNSUPPORTED, "head epilogue: nout=%d (at most 158)", nout);
+    if (wm_floats) *wm_floats = 2LL * C * 9 * 32 * mb;
+    if (wv_floats) *wv_floats = 2LL * C * 9;
+    if (bias_floats) *bias_floats = 32LL * mb;
+    return NLSPN_OK;
+}
+
+int nlspn_head_pack_weights(const float *w_oa, const float *b_oa, const float *w_id, const float *b_id,
+                            const float *w_cf, const float *b_cf, float *wm, float *wv, float *bias, int C, int nout,
+                            void *stream) {
+    int64_t nm = 0, nv = 0, nb = 0;
+    NLSPN_TRY(nlspn_head_packed_size(C, nout, &nm, &nv, &nb));
+    if (!w_oa || !wm || !wv || !bias) return fail(NLSPN_EINVAL, "head epilogue: null pointer");
+    HeadsPackArgs a{w_oa, b_oa, w_id, b_id, w_cf, b_cf, wm, wv, bias, C, nout, (int)nb};
+    const long long n = nm + nv + nb;
+    void *args[] = {&a};
+    return launch_kernel(reinterpret_cast<const void *>(&heads_pack_kernel), dim3((unsigned)((n + 255) / 256)), dim3(256),
+                         args, 0, as_stream(stream), "nlspn_head_pack_weights");
+}
+
+int nlspn_head_epilogue(int dtype, const void *fe1, const void *fd_oa, const void *fd_id, const void *fd_cf,
+                        const float *wm, const float *wv, const float *bias, void *off_aff, void *pred_init,
+                        void *conf, int B, int C, int H, int W, int nout, void *stream) {
+    NLSPN_TRY(check_f32(dtype, "head epilogue"));
+    NLSPN_TRY(check_nonempty(B, H, W));
+    NLSPN_TRY(nlspn_head_packed_size(C, nout, nullptr, nullptr, nullptr));
+    if (!fe1 || !fd_oa || !wm || !wv || !bias || !off_aff) return fail(NLSPN_EINVAL, "head epilogue: null pointer");
+    if ((fd_id == nullptr) != (pred_init == nullptr) || (fd_cf == nullptr) != (conf == nullptr))
+        return fail(NLSPN_EINVAL, "head epilogue: a head's source and output must both be given or both NULL");
+    HeadsArgs a{static_cast<const float *>(fe1), static_cast<const float *>(fd_oa), static_cast<const float *>(fd_id),
+                static_cast<const float *>(fd_cf), wm, wv, bias, static_cast<float *>(off_aff),
+                static_cast<float *>(pred_init), static_cast<float *>(conf), B, C, H, W, nout,
+                (W + kHdTW - 1) / kHdTW, (H + kHdTH - 1) / kHdTH, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                0u, 0u};
+    a.dbg = env_dbg("NLSPN_HEADS_DBG");
+    return launch_heads(a, stream);
+}
+
+int nlspn_head_epilogue_prologue(int dtype, const void *fe1, const void *fd_oa, const void *fd_id, const void *fd_cf,
+                                 const float *wm, const float *wv, const float *bias, const void *dep,
+                                 const float *gamma, void *pred_init, void *conf_out, void *aff_out, void *off_out,
+                                 void *p0, int B, int C, int H, int W, int kh, int kw, int kind, unsigned flags,
+                                 void *stream) {
+    NLSPN_TRY(check_f32(dtype, "head epilogue"));
+    NLSPN_TRY(check_nonempty(B, H, W));
+    if (kh != 3 || kw != 3)
+        return fail(NLSPN_EUNSUPPORTED, "fused head prologue: 3x3 propagation only (k = %dx%d)", kh, kw);
+    NLSPN_TRY(check_kind(kind));
+    const int nout = 3 * 8;
+    NLSPN_TRY(nlspn_head_packed_size(C, nout, nullptr, nullptr, nullptr));
+    if (!fe1 || !fd_oa || !fd_id || !wm || !wv || !bias || !gamma || !pred_init || !aff_out || !off_out || !p0)
+        return fail(NLSPN_EINVAL, "fused head prologue: null pointer");
+    if ((fd_cf == nullptr) != (conf_out == nullptr))
+        return fail(NLSPN_EINVAL, "fused head prologue: cf_fd1 and conf_out must both be given or both NULL");
+    NLSPN_TRY(check_preserve(flags, dep));
+    HeadsArgs a{static_cast<const float *>(fe1), static_cast<const float *>(fd_oa), static_cast<const float *>(fd_id),
+                static_cast<const float *>(fd_cf), wm, wv, bias, nullptr, static_cast<float *>(pred_init),
+                static_cast<float *>(conf_out), B, C, H, W, nout, (W + kHdTW - 1) / kHdTW, (H + kHdTH - 1) / kHdTH,
+                static_cast<const float *>(dep), gamma, static_cast<float *>(aff_out), static_cast<float *>(off_out),
+                static_cast<float *>(p0), kind, flags, 0u};
+    return launch_heads(a, stream);
+}
+
+int nlspn_affinity_normalize(int dtype, const void *aff_raw, int64_t aff_bstride, const float *gamma,
+                             void *aff_out, int B, int K, int H, int W, int kind, void *stream) {
+    NLSPN_TRY(check_storage_dtype(dtype));
+    NLSPN_TRY(check_nonempty(B, H, W));
+    NLSPN_TRY(check_kind(kind));
+    if (!aff_raw || !gamma || !aff_out) return fail(NLSPN_EINVAL, "null pointer");
+    const long long HW = (long long)H * W;
+    NLSPN_TRY(check_batch_stride("aff", aff_bstride, K, HW));
+    const size_t vb = 4 * esize(dtype);
+    const bool vec = HW % 4 == 0 && aff_bstride % 4 == 0 && aligned(aff_raw, vb) && aligned(aff_out, vb);
+    const void *fn = dtype == NLSPN_DTYPE_F32 ? select_affnorm<float>(K, vec) : select_affnorm<__half>(K, vec);
+    if (!fn) return fail(NLSPN_EUNSUPPORTED, "no affinity kernel for K=%d (supported 8, 16, 24, 48)", K);
+    long long bs = aff_bstride, hw = HW;
+    int b = B, k = kind;
+    void *args[] = {(void *)&aff_raw, &bs, (void *)&gamma, &aff_out, &hw, &b, &k};
+    return launch_kernel(fn, dim3(elementwise_grid((long long)B * HW / (vec ? 4 : 1))), dim3(256), args, 0,
+                         as_stream(stream), "nlspn_affinity_normalize");
+}
+
+int nlspn_mdcn_forward(int dtype, const void *input, const void *weight, const void *bias, const void *offset,
+                       const void *mask, void *output, int B, int C, int H, int W, int Cout, int kh, int kw, int sh,
+                       int sw, int ph, int pw, int dh, int dw, int group, int deformable_group, void *stream) {
+    if (dtype != NLSPN_DTYPE_F32 && dtype != NLSPN_DTYPE_F16 && dtype != NLSPN_DTYPE_F64)
+        return fail(NLSPN_EUNSUPPORTED, "dtype %d", dtype);
+    if (!input || !weight || !offset || !mask || !output) return fail(NLSPN_EINVAL, "null required pointer");
+    int Ho = 0, Wo = 0;
+    NLSPN_TRY(check_mdcn(B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, group, deformable_group, &Ho, &Wo));
+    MdcnArgs a{input, weight, bias, offset, mask, output, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw,
+               group, deformable_group, Ho, Wo};
+    const void *fn = dtype == NLSPN_DTYPE_F32   ? reinterpret_cast<const void *>(&mdcn_forward_kernel<float, float>)
+                     : dtype == NLSPN_DTYPE_F64 ? reinterpret_cast<const void *>(&mdcn_forward_kernel<double, double>)
+                                                : reinterpret_cast<const void *>(&mdcn_forward_kernel<__half, float>);
+    void *args[] = {&a};
+    return launch_kernel(fn, dim3(elementwise_grid((long long)B * Cout * Ho * Wo)), dim3(256), args, 0, as_stream(stream),
+                         "nlspn_mdcn_forward");
+}
+
+int nlspn_mdcn_backward(int dtype, const void *input, const void *weight, const void *offset, const void *mask,
+                        const void *grad_output, void *grad_input, void *grad_offset, void *grad_mask,
+                        void *grad_weight, void *grad_bias, int B, int C, int H, int W, int Cout, int kh, int kw,
+                        int sh, int sw, int ph, int pw, int dh, int dw, int group, int deformable_group,
+                        void *stream) {
+    if (dtype != NLSPN_DTYPE_F32 && dtype != NLSPN_DTYPE_F64)
+        return fail(NLSPN_EUNSUPPORTED, "the DCN backward is implemented for float32 and float64");
+    if (!input || !weight || !offset || !mask || !grad_output || !grad_input || !grad_offset || !grad_mask ||
+        !grad_weight)
+        return fail(NLSPN_EINVAL, "null required pointer");
+    int Ho = 0, Wo = 0;
+    NLSPN_TRY(check_mdcn(B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, group, deformable_group, &Ho, &Wo));
+    const long long nw = (long long)Cout * (C / group) * kh * kw + (grad_bias ? Cout : 0);
+    if (nw > 0x7fffffffLL) return fail(NLSPN_EINVAL, "too many weight elements");
+    const long long nd = (long long)B * deformable_group * kh * kw * Ho * Wo;
+    return dtype == NLSPN_DTYPE_F64
+               ? mdcn_backward_impl<double>(input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask,
+                                            grad_weight, grad_bias, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw,
+                                            group, deformable_group, Ho, Wo, nd, nw, as_stream(stream))
+               : mdcn_backward_impl<float>(input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask,
+                                           grad_weight, grad_bias, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw,
+                                           group, deformable_group, Ho, Wo, nd, nw, as_stream(stream));
+}
+
+}  // extern "C"

@@ -125,6 +125,23 @@ def test_resident_engaged_at_c2():
         assert ok and grid == 4 * 63 and block == 576
 
 
+def test_resident_config_matches_plan_table():
+    """On a 256-CU device the library plans what tests/golden/resident_plans.json records
+    (tests/test_planner_cpu.py checks the planner against the same table without a device)."""
+    import json
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if cus != 256:
+        pytest.skip(f"the plan table's rows are for 256 CUs (this device: {cus})")
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "resident_plans.json")) as f:
+        rows = {r["name"]: r for r in json.load(f)["forward"]}
+    for name in ("C1", "C2", "C3", "C5"):
+        r = rows[name]
+        assert r["cus"] == 256 and r["switch"] == "" and r["resident"]
+        ok, grid, block, lds = resident_config(r["B"], r["H"], r["W"], dtype=1 if r["dtype"] == "f16" else 0, T=r["T"],
+                                               kernel=(r["kh"], r["kw"]))
+        assert ok and (grid, block, lds) == (r["grid"][0], r["nt"], r["lds_bytes"]), (name, grid, block, lds)
+
+
 @pytest.mark.parametrize("B,H,W,sigma,dtype,conf,kw", [
     (8, 228, 304, 2.0, torch.float32, True, {}),                        # C2
     (8, 228, 304, 2.0, torch.float32, True, {"always_clip": True}),

@@ -6,53 +6,30 @@ under a given window row pitch and thread->quad mapping.  Offline design tool on
 
 usage: python tools/lds_bank_sim.py [--config nyu|kitti] [--pitch 128 136 ...]"""
 import argparse
+import json
+import os
 import sys
 
 import numpy as np
 
-sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 from nlspn_eccv20_amd.synthetic import synth  # noqa: E402
 
-K, REF, KW, CTL, PADX, RY, RXQ = 8, 4, 3, 8, 4, 8, 2
-LDS = 160 * 1024
+K, REF, KW, CTL, PADX = 8, 4, 3, 8, 4
 
 
-def win_cells(nt):
-    return min((LDS - 4 * CTL - 16 * 11 * nt) // 8 // 4 * 4, 32764)
+def planned_shape(cfg):
+    """The part grid the kernel runs for a bench workload: the C2 / C3 row of the planner's
+    recorded table (tests/golden/resident_plans.json, checked against csrc/nlspn_plan.h by
+    tests/test_planner_cpu.py).  This tool carries no planner of its own."""
+    with open(os.path.join(ROOT, "tests", "golden", "resident_plans.json")) as f:
+        rows = {r["name"]: r for r in json.load(f)["forward"]}
+    r = rows[{"nyu": "C2", "kitti": "C3"}[cfg]]
+    return (r["B"], r["H"], r["W"]), (r["gy"], r["gx"], r["nt"], r["win_cells"])
 
 
-def res_shape(B, H, W, cus=256):
-    """nlspn_capi.hip res_shape (the part grid the kernel runs)."""
-    W4 = W // 4
-    Q = H * W4
-    for Bg in range(min(B, cus), 0, -1):
-        gmax = min(cus // Bg, max(1, Q // 64))
-        best, res = 1e300, None
-        for g in range(gmax, max(1, gmax * 3 // 4) - 1, -1):
-            for gy in range(1, g + 1):
-                if g % gy:
-                    continue
-                gx = g // gy
-                if gy > H or gx > W4:
-                    continue
-                ph, pq = -(-H // gy), -(-W4 // gx)
-                nq = ph * pq
-                nt = -(-nq // 64) * 64
-                if nt > 768:
-                    continue
-                fb = (ph + 2 * RY) * (4 * (pq + 2 * RXQ) + 2 * PADX)
-                if win_cells(nt) < fb:
-                    continue
-                rim = ((ph + 18) * (4.0 * pq + 18) - 4.0 * nq) / 4.0
-                cost = nq + 0.2 * rim
-                if cost < best:
-                    best, res = cost, (Bg, gy, gx, nt)
-        if res:
-            return res
-    raise ValueError("no shape")
-
-
-def part_addresses(offy, offx, H, W, gy, gx, py, px, nt, pitch, order="row"):
+def part_addresses(offy, offx, H, W, gy, gx, py, px, nt, WC, pitch, order="row"):
     """Per thread (nt) and tap-pixel slot (32): the dword address of the footprint's upper
     pair (fwin / fwinB copy) and the pitch; None where the thread holds no quad."""
     W4 = W // 4
@@ -88,7 +65,6 @@ def part_addresses(offy, offx, H, W, gy, gx, py, px, nt, pitch, order="row"):
     WWp = 4 * (wq1 - wq0 + 1)
     WW = pitch if pitch else WWp + 2 * PADX
     assert WWp + 2 * PADX <= WW, (WWp, WW)
-    WC = win_cells(nt)
     assert (rhi - rlo + 1) * WW <= WC, ((rhi - rlo + 1) * WW, WC)
     hl = np.where(valid, hl, rlo)
     wl = np.where(valid, wl, 4 * wq0 - PADX)
@@ -111,8 +87,7 @@ def cycles(addr, act):
 
 
 def simulate(cfg, pitch, parts=8, seed=7240):
-    B, H, W = {"nyu": (8, 228, 304), "kitti": (4, 240, 1216)}[cfg]
-    Bg, gy, gx, nt = res_shape(B, H, W)
+    (B, H, W), (gy, gx, nt, WC) = planned_shape(cfg)
     d = synth(1, H, W, K, seed=seed)
     off = d["off_aff"][0, :2 * K]
     offy, offx = off[0::2], off[1::2]
@@ -120,7 +95,7 @@ def simulate(cfg, pitch, parts=8, seed=7240):
     rng = np.random.default_rng(1)
     for j in rng.choice(gy * gx, size=min(parts, gy * gx), replace=False):
         py, px = divmod(int(j), gx)
-        addr, WW, act = part_addresses(offy, offx, H, W, gy, gx, py, px, nt, pitch)
+        addr, WW, act = part_addresses(offy, offx, H, W, gy, gx, py, px, nt, WC, pitch)
         for wv in range(nt // 64):
             sl = slice(64 * wv, 64 * wv + 64)
             if not act[sl].any():
