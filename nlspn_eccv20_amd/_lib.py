@@ -5,6 +5,14 @@ imported first on purpose: its bundled HIP runtime (soname ``libamdhip64.so.7``)
 must be the one our library binds to, so that torch streams and device pointers
 are valid in our calls.  There is no fallback: if the library is missing the
 product path raises.
+
+``call()`` is the one place the package performs a launching C-ABI call: it enters
+the tensors' device, checks the resident status word where asked, turns tensors into
+pointers and ``STREAM`` into the device's current stream, and raises ``NlspnError``
+on a non-zero return code.  The helpers every wrapper shares (``ptr``, ``stream``,
+``flags``, ``gamma_f32``, ``require_cuda``) live beside it.  ``SIGNATURES`` is the
+hand-written mirror of the header that ``get()`` installs; tests/test_capi_cpu.py
+checks it against the header, argument by argument.
 """
 from __future__ import annotations
 
@@ -133,6 +141,53 @@ def check_resident(device=None) -> None:
             hit = lib.nlspn_resident_status(1)
     if hit:
         raise NlspnError(EABORTED, lib.nlspn_last_error().decode(errors="replace"))
+
+
+STREAM = object()  # call() argument marker: the current stream of the call's device
+_fns = {}
+
+
+def call(name: str, device, *args, resident: bool = False) -> None:
+    """The launching C-ABI call `name` on `device` (a tensor's torch.device).  Arguments are
+    written in the header's order: tensors pass as their data pointers (None as a null
+    pointer), STREAM as the device's current stream, numbers and ctypes.byref() objects
+    as they are.  resident: raise first if an earlier resident launch on the device aborted."""
+    fn = _fns.get(name)
+    if fn is None:
+        fn = _fns[name] = getattr(get(), name)
+    idx = device.index  # of a tensor's torch.device; as an int, torch does not parse the device twice per call
+    with torch.cuda.device(idx):
+        if resident:
+            check_resident()
+        rc = fn(*[a if a.__class__ is int else a.data_ptr() if isinstance(a, torch.Tensor)
+                  else torch.cuda.current_stream(idx).cuda_stream if a is STREAM else a for a in args])
+        if rc != 0:
+            check(rc)
+
+
+def ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def stream(device):
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def flags(preserve_input, always_clip) -> int:
+    return (PRESERVE_INPUT if preserve_input else 0) | (ALWAYS_CLIP if always_clip else 0)
+
+
+def gamma_f32(gamma) -> torch.Tensor:
+    if not torch.is_tensor(gamma):
+        raise TypeError("gamma must be a device tensor (aff_scale_const)")
+    g = gamma.detach().reshape(-1)[:1]
+    return g if g.dtype == torch.float32 else g.float()
+
+
+def require_cuda(name: str, t) -> None:
+    # modulated_deform_conv_cuda.cu:42-46 ("... must be a CUDA tensor")
+    if t is not None and not t.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA tensor")
 
 
 def header_symbols() -> list[str]:

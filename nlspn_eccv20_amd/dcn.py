@@ -15,7 +15,6 @@ from torch.autograd.function import once_differentiable
 from torch.nn.modules.utils import _pair
 
 from . import _lib
-from .propagation import _cuda, _ptr, _stream
 
 _DCN_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.float64: _lib.DTYPE_F64}
 
@@ -31,43 +30,56 @@ def _dcn_dtype(t: torch.Tensor, backward: bool = False) -> int:
 __all__ = ["modulated_deform_conv_forward", "modulated_deform_conv_backward", "ModulatedDeformConvFunction"]
 
 
+def _operands(input, weight, **others) -> None:
+    """The checks both entry points open with (modulated_deform_conv_cuda.cu:42-46)."""
+    if not input.is_contiguous():
+        raise RuntimeError("input tensor has to be contiguous")
+    if not weight.is_contiguous():
+        raise RuntimeError("weight tensor has to be contiguous")
+    for n, t in dict(input=input, weight=weight, **others).items():
+        _lib.require_cuda(n, t)
+
+
+def _same_dtype(input, weight, **others) -> None:
+    for n, t in dict(weight=weight, **others).items():
+        if t is not None and t.dtype != input.dtype:
+            raise RuntimeError(f"{n} dtype {t.dtype} differs from input dtype {input.dtype}")
+
+
+def _out_size(input, weight, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group):
+    """Check the weight against the kernel size and the input's channels; return (Ho, Wo)."""
+    (_, C, H, W), (_, Ckern, kh_, kw_) = input.shape, weight.shape
+    if kh_ != kernel_h or kw_ != kernel_w:
+        raise RuntimeError(f"Input shape and kernel shape wont match: ({kernel_h} x {kernel_w} vs {kh_} x {kw_}).")
+    if C != Ckern * group:
+        raise RuntimeError(f"Input shape and kernel channels wont match: ({C} vs {Ckern * group}).")
+    return ((H + 2 * pad_h - (dilation_h * (kernel_h - 1) + 1)) // stride_h + 1,
+            (W + 2 * pad_w - (dilation_w * (kernel_w - 1) + 1)) // stride_w + 1)
+
+
 def modulated_deform_conv_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride_h, stride_w,
                                   pad_h, pad_w, dilation_h, dilation_w, group, deformable_group, im2col_step):
     """Same signature and checks as modulated_deform_conv_cuda_forward
     (modulated_deform_conv_cuda.cu:19-121); returns (B, Cout, Ho, Wo).  im2col_step is
     accepted for signature compatibility; there is no columns buffer to chunk."""
-    if not input.is_contiguous():
-        raise RuntimeError("input tensor has to be contiguous")
-    if not weight.is_contiguous():
-        raise RuntimeError("weight tensor has to be contiguous")
-    for n, t in (("input", input), ("weight", weight), ("bias", bias), ("offset", offset), ("mask", mask)):
-        _cuda(n, t)
+    _operands(input, weight, bias=bias, offset=offset, mask=mask)
     B, C, H, W = input.shape
-    Cout, Ckern, kh_, kw_ = weight.shape
-    if kh_ != kernel_h or kw_ != kernel_w:
-        raise RuntimeError(f"Input shape and kernel shape wont match: ({kernel_h} x {kernel_w} vs {kh_} x {kw_}).")
-    if C != Ckern * group:
-        raise RuntimeError(f"Input shape and kernel channels wont match: ({C} vs {Ckern * group}).")
-    Ho = (H + 2 * pad_h - (dilation_h * (kernel_h - 1) + 1)) // stride_h + 1
-    Wo = (W + 2 * pad_w - (dilation_w * (kernel_w - 1) + 1)) // stride_w + 1
+    Cout = weight.shape[0]
+    Ho, Wo = _out_size(input, weight, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
+                       group)
     KK = kernel_h * kernel_w
     if tuple(offset.shape) != (B, 2 * deformable_group * KK, Ho, Wo):
         raise RuntimeError(f"offset has shape {tuple(offset.shape)}, expected {(B, 2 * deformable_group * KK, Ho, Wo)}")
     if tuple(mask.shape) != (B, deformable_group * KK, Ho, Wo):
         raise RuntimeError(f"mask has shape {tuple(mask.shape)}, expected {(B, deformable_group * KK, Ho, Wo)}")
-    dt = input.dtype
-    offset, mask, weight = offset.contiguous(), mask.contiguous(), weight.contiguous()
+    offset, mask = offset.contiguous(), mask.contiguous()
     if bias is not None:
         bias = bias.contiguous()
-    for n, t in (("weight", weight), ("bias", bias), ("offset", offset), ("mask", mask)):
-        if t is not None and t.dtype != dt:
-            raise RuntimeError(f"{n} dtype {t.dtype} differs from input dtype {dt}")
-    out = torch.empty((B, Cout, Ho, Wo), dtype=dt, device=input.device)
-    with torch.cuda.device(input.device):
-        _lib.check(_lib.get().nlspn_mdcn_forward(
-            _dcn_dtype(input), _ptr(input), _ptr(weight), _ptr(bias), _ptr(offset), _ptr(mask), _ptr(out),
-            B, C, H, W, Cout, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
-            group, deformable_group, _stream(input.device)))
+    _same_dtype(input, weight, bias=bias, offset=offset, mask=mask)
+    out = torch.empty((B, Cout, Ho, Wo), dtype=input.dtype, device=input.device)
+    _lib.call("nlspn_mdcn_forward", input.device, _dcn_dtype(input), input, weight, bias, offset, mask, out,
+              B, C, H, W, Cout, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
+              group, deformable_group, _lib.STREAM)
     return out
 
 
@@ -79,27 +91,15 @@ def modulated_deform_conv_backward(input, weight, bias, offset, mask, grad_outpu
     grad_weight, grad_bias].  float32 or float64, as the reference dispatches
     (.cu:221).  Like the reference's col2im call (.cuh:371) grad_input uses pad_h for
     the width padding too (identical for square padding)."""
-    if not input.is_contiguous():
-        raise RuntimeError("input tensor has to be contiguous")
-    if not weight.is_contiguous():
-        raise RuntimeError("weight tensor has to be contiguous")
-    for n, t in (("input", input), ("weight", weight), ("bias", bias), ("offset", offset), ("mask", mask),
-                 ("grad_output", grad_output)):
-        _cuda(n, t)
+    _operands(input, weight, bias=bias, offset=offset, mask=mask, grad_output=grad_output)
     dt = _dcn_dtype(input, backward=True)
-    for n, t in (("weight", weight), ("bias", bias), ("offset", offset), ("mask", mask), ("grad_output", grad_output)):
-        if t is not None and t.dtype != input.dtype:
-            raise RuntimeError(f"{n} dtype {t.dtype} differs from input dtype {input.dtype}")
+    _same_dtype(input, weight, bias=bias, offset=offset, mask=mask, grad_output=grad_output)
     B, C, H, W = input.shape
-    Cout, Ckern, kh_, kw_ = weight.shape
+    Cout = weight.shape[0]
     if (C % group) != 0 or (Cout % group) != 0:
         raise RuntimeError(f"channels({C}) and channels_out({Cout}) must divide group({group})")
-    if kh_ != kernel_h or kw_ != kernel_w:
-        raise RuntimeError(f"Input shape and kernel shape wont match: ({kernel_h} x {kernel_w} vs {kh_} x {kw_}).")
-    if C != Ckern * group:
-        raise RuntimeError(f"Input shape and kernel channels wont match: ({C} vs {Ckern * group}).")
-    Ho = (H + 2 * pad_h - (dilation_h * (kernel_h - 1) + 1)) // stride_h + 1
-    Wo = (W + 2 * pad_w - (dilation_w * (kernel_w - 1) + 1)) // stride_w + 1
+    Ho, Wo = _out_size(input, weight, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
+                       group)
     if grad_output.shape[0] != B:
         raise RuntimeError(f"Input shape and grad_out batch wont match: ({B} vs {grad_output.shape[0]}).")
     if grad_output.shape[1] != Cout:
@@ -113,12 +113,10 @@ def modulated_deform_conv_backward(input, weight, bias, offset, mask, grad_outpu
     grad_mask = torch.empty_like(mask)
     grad_weight = torch.empty_like(weight)
     grad_bias = torch.empty_like(bias) if bias is not None else None
-    with torch.cuda.device(input.device):
-        _lib.check(_lib.get().nlspn_mdcn_backward(
-            dt, _ptr(input), _ptr(weight), _ptr(offset), _ptr(mask), _ptr(grad_output),
-            _ptr(grad_input), _ptr(grad_offset), _ptr(grad_mask), _ptr(grad_weight), _ptr(grad_bias),
-            B, C, H, W, Cout, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
-            group, deformable_group, _stream(input.device)))
+    _lib.call("nlspn_mdcn_backward", input.device, dt, input, weight, offset, mask, grad_output,
+              grad_input, grad_offset, grad_mask, grad_weight, grad_bias,
+              B, C, H, W, Cout, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
+              group, deformable_group, _lib.STREAM)
     return [grad_input, grad_offset, grad_mask, grad_weight, grad_bias]
 
 

@@ -40,13 +40,10 @@ _T_TAPS = [[(ky, kx) for ky in ((0, 2) if py else (1,)) for kx in ((0, 2) if px 
            for py in (0, 1) for px in (0, 1)]
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def _layout(layer):
+    lib = _lib.get()  # a query: no device, no launch
     co, cc, tr = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(_lib.get().nlspn_gconv_pack_layout(layer, ctypes.byref(co), ctypes.byref(cc), ctypes.byref(tr)))
+    _lib.check(lib.nlspn_gconv_pack_layout(layer, ctypes.byref(co), ctypes.byref(cc), ctypes.byref(tr)))
     return co.value, cc.value, bool(tr.value)
 
 
@@ -180,11 +177,8 @@ class GruConvs:
     def _run(L, x0, c0, x1=None, c1=0, out=None, ohs=None, ows=None, in_div=1.0, h=None, zb=None, rhb=None,
              qxb=None, hout=None, hc=0):
         B, _, Hi, Wi = x0.shape
-        lib = _lib.get()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)
-        _lib.check(lib.nlspn_gconv(L.layer, _p(x0), c0, _p(x1), c1, _p(L.w), _p(L.b), _p(out), _p(h), _p(zb), _p(rhb),
-                                   _p(qxb), _p(hout), B, Hi, Wi, L.cout, ohs or 0, ows or 0, L.act,
-                                   ctypes.c_float(in_div), hc, stream))
+        _lib.call("nlspn_gconv", x0.device, L.layer, x0, c0, x1, c1, L.w, L.b, out, h, zb, rhb, qxb, hout,
+                  B, Hi, Wi, L.cout, ohs or 0, ows or 0, L.act, in_div, hc, _lib.STREAM)
 
     def _conv_s2(self, L, x, in_div=1.0):
         B, _, Hi, Wi = x.shape
@@ -241,7 +235,6 @@ class GruConvs:
         ohs, ows = (min(crop[0], 2 * Hi), min(crop[1], 2 * Wi)) if crop else (2 * Hi, 2 * Wi)
         g = gamma.detach().reshape(-1)[:1].to(device=x.device, dtype=torch.float32).contiguous()
         y = torch.empty((B, L.cout + 1, ohs, ows), device=x.device, dtype=torch.float32)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(_lib.get().nlspn_gconv_affnorm(_p(x), L.cin, _p(L.w), _p(L.b), _p(y), _p(g), _lib.AFF_KINDS[kind],
-                                                  B, Hi, Wi, L.cout, ohs, ows, L.act, stream))
+        _lib.call("nlspn_gconv_affnorm", x.device, x, L.cin, L.w, L.b, y, g, _lib.AFF_KINDS[kind],
+                  B, Hi, Wi, L.cout, ohs, ows, L.act, _lib.STREAM)
         return y

@@ -26,14 +26,6 @@ from . import _lib
 __all__ = ["head_epilogue", "head_epilogue_prologue", "HeadWeights"]
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def _conv_of(m):
     """The nn.Conv2d of a head (a bare conv, or the first layer of conv_bn_relu /
     cf_dec0's Sequential)."""
@@ -93,12 +85,20 @@ class HeadWeights:
         w = lambda c: None if c is None else c.weight.detach().contiguous()  # noqa: E731
         b = lambda c: None if c is None else c.bias.detach().contiguous()  # noqa: E731
         e.keep = [w(oa), b(oa), w(idc), b(idc), w(cfc), b(cfc)]  # alive until the pack kernel has run
-        with torch.cuda.device(dev):
-            _lib.check(lib.nlspn_head_pack_weights(*[_p(t) for t in e.keep], _p(e.wm), _p(e.wv), _p(e.bias),
-                                                   C, nout, _stream(dev)))
+        _lib.call("nlspn_head_pack_weights", dev, *e.keep, e.wm, e.wv, e.bias, C, nout, _lib.STREAM)
         e.key, e.C, e.nout = key, C, nout
         self._entries[dev] = e
         return e
+
+
+def _sources(fe1, off_aff_fd1, id_fd1, cf_fd1, bad):
+    """The decoder outputs the kernel reads, made contiguous: each present one a float32
+    CUDA tensor of fe1's shape, else `bad(name, tensor, shape)` gives the caller's message."""
+    srcs = (fe1, off_aff_fd1, id_fd1, cf_fd1)
+    for n, t in zip(("fe1", "off_aff_fd1", "id_fd1", "cf_fd1"), srcs):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or t.shape != fe1.shape):
+            raise RuntimeError(bad(n, t, tuple(fe1.shape)))
+    return [None if t is None else t.contiguous() for t in srcs]
 
 
 def head_epilogue(fe1, off_aff_fd1, off_aff_dec0, id_fd1=None, id_dec0=None, cf_fd1=None, cf_dec0=None,
@@ -110,27 +110,18 @@ def head_epilogue(fe1, off_aff_fd1, off_aff_dec0, id_fd1=None, id_dec0=None, cf_
     if (id_fd1 is None) != (idc is None) or (cf_fd1 is None) != (cfc is None):
         raise RuntimeError("each head needs both its decoder output and its convolution")
     weights = (weights or HeadWeights()).get(oa, idc, cfc)  # this device's packed entry
-    srcs = [fe1, off_aff_fd1, id_fd1, cf_fd1]
     B, C, H, W = fe1.shape
     if C != weights.C:
         raise RuntimeError(f"fe1 has {C} channels, the head convolutions expect {weights.C} + {weights.C}")
-    for n, t in zip(("fe1", "off_aff_fd1", "id_fd1", "cf_fd1"), srcs):
-        if t is None:
-            continue
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"{n} must be a float32 CUDA tensor")
-        if tuple(t.shape) != (B, C, H, W):
-            raise RuntimeError(f"{n} must be {(B, C, H, W)} (the _concat crop is done by the caller), got "
-                               f"{tuple(t.shape)}")
-    srcs = [None if t is None else t.contiguous() for t in srcs]
+    srcs = _sources(fe1, off_aff_fd1, id_fd1, cf_fd1, lambda n, t, shape: (
+        f"{n} must be a float32 CUDA tensor" if not t.is_cuda or t.dtype != torch.float32 else
+        f"{n} must be {shape} (the _concat crop is done by the caller), got {tuple(t.shape)}"))
     dev = fe1.device
     off_aff = torch.empty((B, weights.nout, H, W), dtype=torch.float32, device=dev)
     pred_init = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev) if id_fd1 is not None else None
     conf = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev) if cf_fd1 is not None else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.get().nlspn_head_epilogue(
-            _lib.DTYPE_F32, *[_p(t) for t in srcs], _p(weights.wm), _p(weights.wv), _p(weights.bias), _p(off_aff),
-            _p(pred_init), _p(conf), B, C, H, W, weights.nout, _stream(dev)))
+    _lib.call("nlspn_head_epilogue", dev, _lib.DTYPE_F32, *srcs, weights.wm, weights.wv, weights.bias, off_aff,
+              pred_init, conf, B, C, H, W, weights.nout, _lib.STREAM)
     return pred_init, off_aff, conf
 
 
@@ -143,36 +134,26 @@ def head_epilogue_prologue(fe1, off_aff_fd1, off_aff_dec0, id_fd1, id_dec0, dep,
     'confidence' (blended, :328-334, or None), 'p0' (iteration 1's input, :341-348)} —
     what nlspn_propagate's step 1 would produce from the raw head outputs, bit for bit.
     Feed them to propagation.propagate_normalized."""
-    from .propagation import _gamma_f32
     oa, idc, cfc = _conv_of(off_aff_dec0), _conv_of(id_dec0), _conv_of(cf_dec0)
     if (cf_fd1 is None) != (cfc is None) or id_fd1 is None or idc is None:
         raise RuntimeError("the fused prologue needs id_fd1/id_dec0, and cf_fd1 with cf_dec0")
     if oa.out_channels != 24:
         raise RuntimeError("the fused prologue is the 3x3 / K=8 / offset geometry (off_aff_dec0 -> 24 channels)")
-    from . import _lib as L
-    if affinity not in L.AFF_KINDS:
+    if affinity not in _lib.AFF_KINDS:
         raise NotImplementedError(affinity)
     weights = (weights or HeadWeights()).get(oa, idc, cfc)
     B, C, H, W = fe1.shape
-    srcs = [fe1, off_aff_fd1, id_fd1, cf_fd1]
-    for n, t in zip(("fe1", "off_aff_fd1", "id_fd1", "cf_fd1"), srcs):
-        if t is None:
-            continue
-        if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (B, C, H, W):
-            raise RuntimeError(f"{n} must be a float32 CUDA tensor of shape {(B, C, H, W)}")
+    srcs = _sources(fe1, off_aff_fd1, id_fd1, cf_fd1,
+                    lambda n, t, shape: f"{n} must be a float32 CUDA tensor of shape {shape}")
     if preserve_input and (dep is None or tuple(dep.shape) != (B, 1, H, W)):
         raise RuntimeError("preserve_input requires dep of shape (B, 1, H, W)")
-    srcs = [None if t is None else t.contiguous() for t in srcs]
     dep = None if dep is None else dep.contiguous().float()
-    g = _gamma_f32(gamma)
+    g = _lib.gamma_f32(gamma)
     dev = fe1.device
     e = lambda c: torch.empty((B, c, H, W), dtype=torch.float32, device=dev)  # noqa: E731
     out = {"pred_init": e(1), "offset": e(18), "aff": e(9), "confidence": e(1) if cf_fd1 is not None else None,
            "p0": e(1)}
-    flags = (L.PRESERVE_INPUT if preserve_input else 0) | (L.ALWAYS_CLIP if always_clip else 0)
-    with torch.cuda.device(dev):
-        L.check(L.get().nlspn_head_epilogue_prologue(
-            L.DTYPE_F32, *[_p(t) for t in srcs], _p(weights.wm), _p(weights.wv), _p(weights.bias), _p(dep), _p(g),
-            _p(out["pred_init"]), _p(out["confidence"]), _p(out["aff"]), _p(out["offset"]), _p(out["p0"]),
-            B, C, H, W, 3, 3, L.AFF_KINDS[affinity], flags, _stream(dev)))
+    _lib.call("nlspn_head_epilogue_prologue", dev, _lib.DTYPE_F32, *srcs, weights.wm, weights.wv, weights.bias, dep, g,
+              out["pred_init"], out["confidence"], out["aff"], out["offset"], out["p0"],
+              B, C, H, W, 3, 3, _lib.AFF_KINDS[affinity], _lib.flags(preserve_input, always_clip), _lib.STREAM)
     return out

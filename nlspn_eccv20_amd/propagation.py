@@ -28,6 +28,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._lib import STREAM, gamma_f32 as _gamma_f32, require_cuda as _cuda
+from ._lib import ptr as _ptr, stream as _stream  # noqa: F401  (raw-call helpers for bench.py and the tools)
 
 __all__ = [
     "affinity_normalization", "off_insert", "prop_step", "propagate", "PropagationPlan",
@@ -42,20 +44,6 @@ def _dtype_code(t: torch.Tensor) -> int:
     if t.dtype == torch.float16:
         return _lib.DTYPE_F16
     raise TypeError(f"NLSPN propagation supports float32 and float16 storage, got {t.dtype}")
-
-
-def _cuda(name: str, t: Optional[torch.Tensor]) -> None:
-    # modulated_deform_conv_cuda.cu:42-46 ("... must be a CUDA tensor")
-    if t is not None and not t.is_cuda:
-        raise RuntimeError(f"{name} must be a CUDA tensor")
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream(device: torch.device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _planes(name: str, t: torch.Tensor, B: int, C: Optional[int], H: int, W: int) -> int:
@@ -92,11 +80,20 @@ def _torch_ops():
     return _OPS or None
 
 
-def _gamma_f32(gamma) -> torch.Tensor:
-    if not torch.is_tensor(gamma):
-        raise TypeError("gamma must be a device tensor (aff_scale_const)")
-    g = gamma.detach().reshape(-1)[:1]
-    return g if g.dtype == torch.float32 else g.float()
+def _optional_planes(ref_name: str, ref: torch.Tensor, *named) -> None:
+    """The optional (B, 1, H, W) planes (name, tensor) of a call: contiguous, of `ref`'s
+    shape and dtype."""
+    B, _, H, W = ref.shape
+    for n, t in named:
+        if t is not None:
+            _planes(n, t, B, 1, H, W)
+            if not t.is_contiguous() or t.dtype != ref.dtype:
+                raise RuntimeError(f"{n} must be contiguous with {ref_name}'s dtype")
+
+
+def _result(pred, pred_inter, **rest) -> dict:
+    """The section's output dict: pred_inter as the list of its T views and as one tensor."""
+    return {"pred": pred, "pred_inter": list(pred_inter.unbind(0)), **rest, "pred_inter_tensor": pred_inter}
 
 
 # -------------------------------------------------------------- functional ops
@@ -108,10 +105,8 @@ def _affinity_normalization(aff: torch.Tensor, gamma: torch.Tensor, kind: str) -
     bs = _planes("aff", aff, B, K, H, W)
     g = _gamma_f32(gamma)
     out = torch.empty((B, K + 1, H, W), dtype=aff.dtype, device=aff.device)
-    with torch.cuda.device(aff.device):
-        _lib.check(_lib.get().nlspn_affinity_normalize(
-            _dtype_code(aff), _ptr(aff), bs, _ptr(g), _ptr(out), B, K, H, W, _lib.AFF_KINDS[kind],
-            _stream(aff.device)))
+    _lib.call("nlspn_affinity_normalize", aff.device, _dtype_code(aff), aff, bs, g, out, B, K, H, W,
+              _lib.AFF_KINDS[kind], STREAM)
     return out
 
 
@@ -143,12 +138,9 @@ def _affnorm_backward(aff, gamma, g_out, kind, want_gamma=True):
     g_raw = torch.empty((B, K, H, W), **f32)
     want_g = kind == "TGASS" and want_gamma
     g_gamma = torch.empty(1, **f32) if want_g else None
-    lib = _lib.get()
-    ws = torch.empty(max(1, lib.nlspn_affinity_normalize_backward_workspace_bytes(B, K, H, W) // 4), **f32)
-    with torch.cuda.device(aff.device):
-        _lib.check(lib.nlspn_affinity_normalize_backward(
-            _lib.DTYPE_F32, _ptr(aff), _planes("aff", aff, B, K, H, W), _ptr(_gamma_f32(gamma)), _ptr(g_out),
-            _ptr(g_raw), _ptr(g_gamma), _ptr(ws), B, K, H, W, _lib.AFF_KINDS[kind], _stream(aff.device)))
+    ws = torch.empty(max(1, _lib.get().nlspn_affinity_normalize_backward_workspace_bytes(B, K, H, W) // 4), **f32)
+    _lib.call("nlspn_affinity_normalize_backward", aff.device, _lib.DTYPE_F32, aff, _planes("aff", aff, B, K, H, W),
+              _gamma_f32(gamma), g_out, g_raw, g_gamma, ws, B, K, H, W, _lib.AFF_KINDS[kind], STREAM)
     if g_gamma is not None:
         g_gamma = g_gamma.reshape(gamma.shape).to(gamma.dtype)
     return g_raw, g_gamma
@@ -186,11 +178,7 @@ def _prop_step(feat, confidence, dep, aff, offset, kernel, offset_layout, preser
     _planes("feat", feat, B, 1, H, W)
     if not feat.is_contiguous():
         raise RuntimeError("input tensor has to be contiguous")
-    for n, t in (("confidence", confidence), ("dep", dep)):
-        if t is not None:
-            _planes(n, t, B, 1, H, W)
-            if t.dtype != feat.dtype or not t.is_contiguous():
-                raise RuntimeError(f"{n} must be contiguous with feat's dtype")
+    _optional_planes("feat", feat, ("confidence", confidence), ("dep", dep))
     if preserve_input and dep is None:
         raise RuntimeError("preserve_input requires dep")
     abs_ = _planes("aff", aff, B, K + 1, H, W)
@@ -200,11 +188,8 @@ def _prop_step(feat, confidence, dep, aff, offset, kernel, offset_layout, preser
         obs = _planes("offset", offset, B, 2 * K if layout == _lib.OFF_RAW else 2 * (K + 1), H, W)
     if out is None:
         out = torch.empty_like(feat)
-    flags = (_lib.PRESERVE_INPUT if preserve_input else 0) | (_lib.ALWAYS_CLIP if always_clip else 0)
-    with torch.cuda.device(feat.device):
-        _lib.check(_lib.get().nlspn_prop_step(
-            _dtype_code(feat), _ptr(feat), _ptr(confidence), _ptr(dep), _ptr(aff), abs_, _ptr(offset), obs,
-            layout, _ptr(out), _ptr(pred_out), B, H, W, kh, kw, flags, _stream(feat.device)))
+    _lib.call("nlspn_prop_step", feat.device, _dtype_code(feat), feat, confidence, dep, aff, abs_, offset, obs,
+              layout, out, pred_out, B, H, W, kh, kw, _lib.flags(preserve_input, always_clip), STREAM)
     return out
 
 
@@ -242,15 +227,11 @@ def _step_backward(feat, conf, dep, aff, off, g_out, kh, kw, preserve, clip):
     g_conf = torch.empty((B, 1, H, W), **f32) if conf is not None else None
     g_aff = torch.empty((B, K + 1, H, W), **f32)
     g_off = torch.empty((B, 2 * K, H, W), **f32) if off is not None else None
-    lib = _lib.get()
-    ws = torch.empty(lib.nlspn_prop_step_backward_workspace_bytes(B, H, W) // 4, **f32)
-    flags = (_lib.PRESERVE_INPUT if preserve else 0) | (_lib.ALWAYS_CLIP if clip else 0)
-    with torch.cuda.device(feat.device):
-        _lib.check(lib.nlspn_prop_step_backward(
-            _lib.DTYPE_F32, _ptr(feat), _ptr(conf), _ptr(dep), _ptr(aff), _planes("aff", aff, B, K + 1, H, W),
-            _ptr(off), _planes("offset", off, B, 2 * K, H, W) if off is not None else 0,
-            _ptr(g_out.contiguous()), _ptr(g_feat), _ptr(g_conf), _ptr(g_aff), _ptr(g_off), _ptr(ws),
-            B, H, W, kh, kw, flags, _stream(feat.device)))
+    ws = torch.empty(_lib.get().nlspn_prop_step_backward_workspace_bytes(B, H, W) // 4, **f32)
+    abs_ = _planes("aff", aff, B, K + 1, H, W)
+    obs = _planes("offset", off, B, 2 * K, H, W) if off is not None else 0
+    _lib.call("nlspn_prop_step_backward", feat.device, _lib.DTYPE_F32, feat, conf, dep, aff, abs_, off, obs,
+              g_out.contiguous(), g_feat, g_conf, g_aff, g_off, ws, B, H, W, kh, kw, _lib.flags(preserve, clip), STREAM)
     return g_feat, g_conf, g_aff, g_off
 
 
@@ -309,11 +290,7 @@ def _propagate_args(pred_init, dep, confidence, aff, offset, gamma, kernel, prop
         raise AssertionError("ch_f must equal pred_init.shape[1] == 1 (nlspnmodel.py:318)")
     _planes("pred_init", pred_init, B, 1, H, W)
     dt = pred_init.dtype
-    for n, t in (("dep", dep), ("confidence", confidence)):
-        if t is not None:
-            _planes(n, t, B, 1, H, W)
-            if not t.is_contiguous() or t.dtype != dt:
-                raise RuntimeError(f"{n} must be contiguous with pred_init's dtype")
+    _optional_planes("pred_init", pred_init, ("dep", dep), ("confidence", confidence))
     if not pred_init.is_contiguous():
         raise RuntimeError("pred_init must be contiguous")
     if preserve_input and dep is None:
@@ -322,12 +299,10 @@ def _propagate_args(pred_init, dep, confidence, aff, offset, gamma, kernel, prop
     obs = _planes("offset", offset, B, 2 * K, H, W) if offset is not None else 0
     if aff.dtype != dt or (offset is not None and offset.dtype != dt):
         raise RuntimeError("aff/offset must have pred_init's dtype")
-    flags = (_lib.PRESERVE_INPUT if preserve_input else 0) | (_lib.ALWAYS_CLIP if always_clip else 0)
     g = _gamma_f32(gamma)
-    args = (_dtype_code(pred_init), _ptr(pred_init), _ptr(dep), _ptr(confidence), _ptr(aff), abs_,
-            _ptr(offset), obs, _ptr(g), _ptr(outs["pred_inter"]), _ptr(outs["pred"]), _ptr(outs["aff"]),
-            _ptr(outs["offset"]), _ptr(outs["confidence"]), _ptr(outs["workspace"]),
-            B, H, W, kh, kw, int(prop_time), _lib.AFF_KINDS[affinity], flags)
+    args = (_dtype_code(pred_init), pred_init, dep, confidence, aff, abs_, offset, obs, g, outs["pred_inter"],
+            outs["pred"], outs["aff"], outs["offset"], outs["confidence"], outs["workspace"],
+            B, H, W, kh, kw, int(prop_time), _lib.AFF_KINDS[affinity], _lib.flags(preserve_input, always_clip))
     return args, g
 
 
@@ -347,9 +322,8 @@ class _PropagateFn(torch.autograd.Function):
                               confidence is not None)
         args, _ = _propagate_args(pred_init, dep, confidence, aff, offset, gamma, kernel, prop_time, affinity,
                                   preserve_input, always_clip, outs)
-        with torch.cuda.device(pred_init.device):
-            _lib.check_resident()  # an earlier resident launch that aborted raises here
-            _lib.check(_lib.get().nlspn_propagate(*args, _stream(pred_init.device)))
+        # resident: an earlier resident launch that aborted raises here
+        _lib.call("nlspn_propagate", pred_init.device, *args, STREAM, resident=True)
         ctx.cfg = (kh, kw, int(prop_time), affinity, preserve_input, always_clip)
         # an unused output's gradient arrives as None, not as a zero-filled tensor: a loss
         # on `pred` alone then neither fills nor reads the (T, B, 1, H, W) pred_inter
@@ -398,18 +372,12 @@ def _section_backward(pred_init, dep, conf, aff, off, gamma, pred_inter, aff_nor
         g_off = torch.empty((B, 2 * K, H, W), **f32) if off is not None else None
         gbs = 0
     g_gamma = torch.zeros(1, **f32)
-    lib = _lib.get()
-    ws = torch.empty(lib.nlspn_backward_workspace_bytes(B, H, W, kh, kw) // 4, **f32)
-    g = _gamma_f32(gamma)
-    flags = (_lib.PRESERVE_INPUT if preserve else 0) | (_lib.ALWAYS_CLIP if clip else 0)
+    ws = torch.empty(_lib.get().nlspn_backward_workspace_bytes(B, H, W, kh, kw) // 4, **f32)
     abs_ = _planes("aff", aff, B, K, H, W)
     obs = _planes("offset", off, B, 2 * K, H, W) if off is not None else 0
-    with torch.cuda.device(dev):
-        _lib.check(lib.nlspn_propagate_backward(
-            _lib.DTYPE_F32, _ptr(pred_init), _ptr(dep), _ptr(conf), _ptr(aff), abs_, _ptr(off), obs, _ptr(g),
-            _ptr(pred_inter), _ptr(aff_norm), _ptr(conf_eff), _ptr(g_pred), _ptr(g_inter), _ptr(g_pi),
-            _ptr(g_conf), _ptr(g_aff), gbs, _ptr(g_off), gbs, _ptr(g_gamma), _ptr(ws), B, H, W, kh, kw, T,
-            _lib.AFF_KINDS[affinity], flags, _stream(dev)))
+    _lib.call("nlspn_propagate_backward", dev, _lib.DTYPE_F32, pred_init, dep, conf, aff, abs_, off, obs,
+              _gamma_f32(gamma), pred_inter, aff_norm, conf_eff, g_pred, g_inter, g_pi, g_conf, g_aff, gbs, g_off, gbs,
+              g_gamma, ws, B, H, W, kh, kw, T, _lib.AFF_KINDS[affinity], _lib.flags(preserve, clip), STREAM)
     g_gamma = g_gamma.reshape(gamma.shape).to(gamma.dtype) if affinity == "TGASS" else None
     return g_pi, g_conf, g_aff, g_off, g_gamma, g_oa
 
@@ -458,8 +426,7 @@ def propagate(pred_init: torch.Tensor, dep: Optional[torch.Tensor], confidence: 
     pred, pred_inter, aff_o, off_o, conf_o = _PropagateFn.apply(
         pred_init, dep, confidence, aff, offset, gamma, prop_time, affinity, kernel, preserve_input, always_clip,
         return_offset, packed)
-    return {"pred": pred, "pred_inter": list(pred_inter.unbind(0)), "offset": off_o, "aff": aff_o,
-            "confidence": conf_o, "pred_inter_tensor": pred_inter}
+    return _result(pred, pred_inter, offset=off_o, aff=aff_o, confidence=conf_o)
 
 
 def propagate_normalized(p0: torch.Tensor, dep: Optional[torch.Tensor], confidence: Optional[torch.Tensor],
@@ -488,13 +455,9 @@ def propagate_normalized(p0: torch.Tensor, dep: Optional[torch.Tensor], confiden
     pred = torch.empty((B, 1, H, W), **kw_)
     ws = torch.empty(_lib.get().nlspn_workspace_bytes(_dtype_code(p0), B, H, W) // 4, dtype=torch.int32,
                      device=p0.device)
-    flags = (_lib.PRESERVE_INPUT if preserve_input else 0) | (_lib.ALWAYS_CLIP if always_clip else 0)
-    with torch.cuda.device(p0.device):
-        _lib.check_resident()
-        _lib.check(_lib.get().nlspn_propagate_normalized(
-            _dtype_code(p0), _ptr(p0), _ptr(dep), _ptr(confidence), _ptr(aff), _ptr(offset), _ptr(pred_inter),
-            _ptr(pred), _ptr(ws), B, H, W, kh, kw, T, flags, _stream(p0.device)))
-    return {"pred": pred, "pred_inter": list(pred_inter.unbind(0)), "pred_inter_tensor": pred_inter}
+    _lib.call("nlspn_propagate_normalized", p0.device, _dtype_code(p0), p0, dep, confidence, aff, offset, pred_inter,
+              pred, ws, B, H, W, kh, kw, T, _lib.flags(preserve_input, always_clip), STREAM, resident=True)
+    return _result(pred, pred_inter)
 
 
 class PropagationPlan:
@@ -510,21 +473,17 @@ class PropagationPlan:
         self.device = pred_init.device
         self.outputs = _alloc_outputs(pred_init, kh * kw - 1, prop_time, offset is not None and return_offset,
                                       confidence is not None)
-        args, g = _propagate_args(pred_init, dep, confidence, aff, offset, gamma, kernel, prop_time, affinity,
-                                  preserve_input, always_clip, self.outputs)
-        self._keep = (pred_init, dep, confidence, aff, offset, g)  # buffers baked into the graph
+        self._keep, _ = _propagate_args(pred_init, dep, confidence, aff, offset, gamma, kernel, prop_time, affinity,
+                                        preserve_input, always_clip, self.outputs)  # buffers baked into the graph
         self._plan = ctypes.c_void_p()
         self._lib = _lib.get()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.nlspn_plan_create(ctypes.byref(self._plan), *args))
+        _lib.call("nlspn_plan_create", self.device, ctypes.byref(self._plan), *self._keep)
 
     def replay(self) -> dict:
-        with torch.cuda.device(self.device):
-            _lib.check_resident()  # an earlier resident launch that aborted raises here
-            _lib.check(self._lib.nlspn_plan_launch(self._plan, _stream(self.device)))
+        # resident: an earlier resident launch that aborted raises here
+        _lib.call("nlspn_plan_launch", self.device, self._plan, STREAM, resident=True)
         o = self.outputs
-        return {"pred": o["pred"], "pred_inter": list(o["pred_inter"].unbind(0)), "offset": o["offset"],
-                "aff": o["aff"], "confidence": o["confidence"], "pred_inter_tensor": o["pred_inter"]}
+        return _result(o["pred"], o["pred_inter"], offset=o["offset"], aff=o["aff"], confidence=o["confidence"])
 
     def check(self) -> None:
         """Wait for this device's queued work, then raise RuntimeError if a resident

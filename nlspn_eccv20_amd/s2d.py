@@ -11,18 +11,12 @@ layers from it in torch.  The sparse depth is data (no gradient), as in training
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.nn.functional as F
 
 from . import _lib
 
 __all__ = ["s2d_front"]
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _run(dep, w1, b1, w2, b2, want_pyr):
@@ -38,10 +32,7 @@ def _run(dep, w1, b1, w2, b2, want_pyr):
     dep, w1, b1, w2, b2 = (t.contiguous() for t in (dep, w1, b1, w2, b2))
     out = torch.empty((B, 17, H, W), dtype=torch.float32, device=dep.device)
     pyr = torch.empty((B, 6, H, W), dtype=torch.float32, device=dep.device) if want_pyr else None
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    with torch.cuda.device(dep.device):
-        _lib.check(_lib.get().nlspn_s2d_pyramid(_lib.DTYPE_F32, p(dep), p(w1), p(b1), p(w2), p(b2), p(out), p(pyr),
-                                                B, H, W, _stream(dep.device)))
+    _lib.call("nlspn_s2d_pyramid", dep.device, _lib.DTYPE_F32, dep, w1, b1, w2, b2, out, pyr, B, H, W, _lib.STREAM)
     return out, pyr
 
 

@@ -2,6 +2,7 @@
 the library loads, exports every symbol include/nlspn_prop.h declares, and rejects
 bad arguments with reference-style errors before touching the device."""
 import ctypes
+import re
 import subprocess
 import types
 
@@ -24,6 +25,47 @@ def test_library_exports_header_symbols():
     assert set(_lib.SIGNATURES) == set(declared)  # ctypes bindings cover the whole header
     for s in declared:
         assert getattr(lib, s) is not None
+
+
+def _header_declarations():
+    """{name: (return type class, [argument type classes])} of include/nlspn_prop.h.  A type
+    class is the C scalar's name, 'ptr' for any pointer (nlspn_plan_t is one), 'str' for
+    a `const char *` return."""
+    text = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
+
+    def cls(decl, named):
+        words = re.findall(r"\w+|\*", decl)
+        if named and words[-1] != "*" and len(words) > 1:
+            words = words[:-1]  # the parameter's name
+        words = [w for w in words if w != "const"]
+        if "*" in words or "nlspn_plan_t" in words:
+            return "str" if words[0] == "char" and not named else "ptr"
+        assert words in (["int"], ["unsigned"], ["int64_t"], ["size_t"], ["float"]), decl
+        return words[0]
+
+    decls = {}
+    for ret, name, params in re.findall(r"([\w \t*]+?)\b(nlspn_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        params = [] if params.strip() == "void" else params.split(",")
+        decls[name] = (cls(ret, False), [cls(p, True) for p in params])
+    return decls
+
+
+def test_signature_table_matches_header():
+    """_lib.SIGNATURES against every declaration of the header: the argument count and
+    each argument's type class (a wrong arity, or c_int where the header has int64_t,
+    would be silent undefined behaviour)."""
+    scalars = {ctypes.c_int: "int", ctypes.c_uint: "unsigned", ctypes.c_int64: "int64_t", ctypes.c_size_t: "size_t",
+               ctypes.c_float: "float", ctypes.c_char_p: "str"}
+
+    def cls(t):
+        return "ptr" if t is ctypes.c_void_p or issubclass(t, ctypes._Pointer) else scalars[t]
+
+    decls = _header_declarations()
+    assert sorted(decls) == _lib.header_symbols() and len(decls) >= 30
+    used = {cls(t) for _, args in _lib.SIGNATURES.values() for t in args}
+    assert used == {"int", "unsigned", "int64_t", "float", "ptr"}  # every class is exercised
+    for name, (res, args) in _lib.SIGNATURES.items():
+        assert (cls(res), [cls(t) for t in args]) == decls[name], name
 
 
 def test_abi_version_and_workspace():

@@ -19,14 +19,14 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def _model(H, W, seed=0, hc=128, K=8):
+def _model(H, W, seed=0, hc=128, K=8, dev=DEV):
     args = types.SimpleNamespace(prop_kernel=3, affinity="TGASS", affinity_gamma=0.5, prop_time=6,
                                  preserve_input=True, always_clip=False, conf_prop=True, offset=True,
                                  network="resnet34", from_scratch=True, zero_init_aff=False, use_GRU=True,
                                  use_S2D=False, GRU_hidden_dim=hc, GRU_input_dim=hc, lr=1e-3, max_depth=10.0,
                                  patch_height=H, patch_width=W, model_name="NLSPN")
     torch.manual_seed(seed)
-    m = NLSPNModel(args).to(DEV).eval()
+    m = NLSPNModel(args).to(dev).eval()
     # non-trivial biases and weights of a trained scale (the reference's init leaves small ones)
     with torch.no_grad():
         for mod in (m.encode_dep, m.encode_aff, m.GRU, m.decode_aff):
@@ -87,6 +87,33 @@ def test_gru_mode_section_native_vs_modules():
     for a, b in zip(o["pred_inter"], r["pred_inter"]):
         assert float(torch.sqrt(torch.mean((a.double() - b.double()) ** 2))) <= 1e-4
     assert np.isfinite(o["pred"].cpu().numpy()).all()
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
+def test_gru_mode_native_on_a_device_other_than_the_current_one():
+    """Model and inputs on cuda:1 while cuda:0 is current: the native convolutions launch on
+    the tensors' device (attributes, CU count, stream and pointers alike), bit-equal to the
+    same call made with cuda:1 current."""
+    B, H, W, dev = 1, 24, 32, "cuda:1"
+    assert torch.cuda.current_device() == 0
+    m = _model(H, W, seed=2, dev=dev)
+    m.args.prop_time = 3
+    g = torch.Generator(device=dev).manual_seed(6)
+    pred_init = torch.rand((B, 1, H, W), device=dev, generator=g) * 10
+    dep = pred_init * (torch.rand((B, 1, H, W), device=dev, generator=g) < 0.05)
+    off_aff = torch.randn((B, 24, H, W), device=dev, generator=g)
+    conf = torch.rand((B, 1, H, W), device=dev, generator=g)
+    with torch.no_grad():
+        o = m.propagate_heads(pred_init, off_aff, conf, dep)
+        assert torch.device(dev) in m._gru_convs._entries  # the native path packed its weights: it ran
+        with torch.cuda.device(1):
+            r = m.propagate_heads(pred_init, off_aff, conf, dep)
+    assert torch.cuda.current_device() == 0
+    for k in ("pred", "aff"):
+        assert o[k].device == torch.device(dev) and torch.equal(o[k], r[k]), k
+    for a, b in zip(o["pred_inter"], r["pred_inter"]):
+        assert torch.equal(a, b)
+    assert torch.isfinite(o["pred"]).all()
 
 
 @pytest.mark.parametrize("kind", ["AS", "ASS", "TC", "TGASS"])

@@ -10,7 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nlspn_eccv20_amd import _lib  # noqa: E402
-from nlspn_eccv20_amd.propagation import PropagationPlan, _alloc_outputs, _propagate_args, _stream  # noqa: E402
+from nlspn_eccv20_amd.propagation import PropagationPlan, _alloc_outputs, _propagate_args  # noqa: E402
 from nlspn_eccv20_amd.synthetic import synth  # noqa: E402
 
 
@@ -23,11 +23,9 @@ def main(B=8, H=228, W=304, T=18, steps=200):
     plan = PropagationPlan(*ins, prop_time=T)
     outs = _alloc_outputs(ins[0], 8, T, True, True)
     args, _ = _propagate_args(*ins, (3, 3), T, "TGASS", True, False, outs)
-    lib = _lib.get()
-    st = _stream(dev)
 
     def direct():
-        _lib.check(lib.nlspn_propagate(*args, st))
+        _lib.call("nlspn_propagate", dev, *args, _lib.STREAM)
 
     for name, fn in (("graph", plan.replay), ("direct", direct), ("graph", plan.replay), ("direct", direct)):
         for _ in range(10):

@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("NLSPN_LIB_PATH", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                      "nlspn_eccv20_amd", "lib", "exp", "libnlspn_hip_exp.so"))
 from nlspn_eccv20_amd import _lib  # noqa: E402
-from nlspn_eccv20_amd.propagation import _alloc_outputs, _propagate_args, _stream  # noqa: E402
+from nlspn_eccv20_amd.propagation import _alloc_outputs, _propagate_args  # noqa: E402
 from nlspn_eccv20_amd.synthetic import synth  # noqa: E402
 
 
@@ -50,7 +50,7 @@ def main(config="nyu", reps=5, bg=None, out=None):
     outs = _alloc_outputs(ins[0], K, T, True, True)
     args, _ = _propagate_args(*ins, kern, T, "TGASS", True, False, outs)
     for _ in range(reps):
-        _lib.check(lib.nlspn_propagate(*args, _stream(dev)))
+        _lib.call("nlspn_propagate", dev, *args, _lib.STREAM)
     torch.cuda.synchronize()
     os.environ.pop("NLSPN_RES_DBG")
     HW = H * W
