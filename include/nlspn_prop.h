@@ -444,6 +444,62 @@ int nlspn_gconv_affnorm(const float *x0, int c0, const float *wpk, const float *
                         const float *gamma, int kind, int B, int Hi, int Wi, int K, int ohs, int ows, int act,
                         void *stream);
 
+/*
+ * Backward of the GRU-mode convolutions (training through encode_dep -> ConvGRU ->
+ * decode_aff, nlspnmodel.py:365-373; replaces the autograd of the torch/MIOpen modules).
+ * f32 NCHW, no double backward.  csrc/nlspn_gconv_bwd.h; nlspn_eccv20_amd/gru.py drives them.
+ *
+ * Data gradient: a forward launch of the adjoint layer kind on adjoint-packed weights, with
+ * the epilogue  dx = act'(ysave) * scale * sum (+ add).  Presets:
+ *   NLSPN_GC_DG_T2 / _T2_C16   adjoint of a stride-2 conv (weights packed as the transposed
+ *       conv of the same (Cout, Cin, 3, 3) tensor; Ho x Wo = the conv's input size, at most one
+ *       row / column less than 2 Hg x 2 Wg)
+ *   NLSPN_GC_DG_S2 / _S2_C16   adjoint of a stride-2 transposed conv (its (Cin, Cout, 3, 3)
+ *       tensor packed as a conv's; the gradient g may be stored cropped, Hg x Wg <= 2 Ho x 2 Wo:
+ *       the rows / columns past the crop read as zeros)
+ *   NLSPN_GC_DG_S1             adjoint of a stride-1 conv (taps flipped, channels transposed)
+ * g: (B, cg, Hg, Wg).  Output channels [0, split) go to dx0 (B, split, Ho, Wo), [split, cout) to
+ * dx1 (null when split = cout); add0 / add1 (optional, laid out as dx0 / dx1, may alias them)
+ * are added.  act / ysave: the activation of the layer whose OUTPUT dx is the gradient of, and
+ * that saved output (B, cout, Ho, Wo): ReLU y > 0, Tanh 1 - y^2 (split = cout then).  One
+ * source only: a two-source chunk that straddles its sources would read zeros.
+ *
+ * Weight and bias gradient: dW[cs][cl][ky][kx] = scale * sum s[b, cs, sy, sx] * l[b, cl, stride
+ * sy - 1 + ky, stride sx - 1 + kx] with s the SMALL tensor (B, Cs, Hs, Ws) and l the LARGE one
+ * (B, c0 + c1, Hl, Wl) = l0 then l1 (c1 may be 0; c0 % 16 == 0 otherwise), zero outside its
+ * stored size.  A conv: s = output gradient, l = input; a transposed conv: s = input, l =
+ * output gradient; either way dw is the module's own weight layout (Cs, c0 + c1, 3, 3).  db
+ * (optional): the per-channel sum of s, or of l0 with bias_from_large.  K (pixels) is split
+ * over workgroups that write f32 slabs into the workspace
+ * (nlspn_gconv_wgrad_workspace_bytes); a second launch sums them in a fixed order: no
+ * atomics, bit-reproducible.
+ *
+ * ConvGRU: nlspn_gconv_gru_train is the NLSPN_GC_GRU1 (stage 1: x0 = h, x1 = x, also stores r
+ * into rb) / NLSPN_GC_GRU2 (stage 2: x0 = r*h, also stores q into qb) launch of nlspn_gconv,
+ * bit-identical in its other outputs.  nlspn_gconv_gru_gates_backward: stage 1 du_q = dh' z
+ * (1 - q^2), du_z = dh' (q - h) z (1 - z) (duzr: (B, 2 hc, H, W) = [du_z, du_r]); stage 2 du_r =
+ * d(rh) h r (1 - r), dh = dh' (1 - z) + d(rh) r; stage 0 a plain activation derivative, duq =
+ * dhn * act'(z) on B * hc * H * W elements.
+ */
+#define NLSPN_GC_DG_T2 32
+#define NLSPN_GC_DG_T2_C16 33
+#define NLSPN_GC_DG_S2 34
+#define NLSPN_GC_DG_S2_C16 35
+#define NLSPN_GC_DG_S1 36
+int nlspn_gconv_dgrad(int layer, const float *g, int cg, const float *wpk, const float *ysave, const float *add0,
+                      const float *add1, float *dx0, float *dx1, int split, int B, int Hg, int Wg, int cout, int Ho,
+                      int Wo, int act, float scale, void *stream);
+size_t nlspn_gconv_wgrad_workspace_bytes(int stride, int Cs, int Cl, int B, int Hs, int Ws, int Hl, int Wl);
+int nlspn_gconv_wgrad(int stride, const float *s, int Cs, const float *l0, int c0, const float *l1, int c1, float *dw,
+                      float *db, int bias_from_large, float scale, void *workspace, int64_t workspace_bytes, int B,
+                      int Hs, int Ws, int Hl, int Wl, void *stream);
+int nlspn_gconv_gru_train(int stage, const float *x0, const float *x1, int c1, const float *wpk, const float *bias,
+                          const float *h, float *zb, float *rhb, float *qxb, float *hout, float *rb, float *qb, int B,
+                          int H, int W, int hc, void *stream);
+int nlspn_gconv_gru_gates_backward(int stage, const float *dhn, const float *z, const float *r, const float *q,
+                                   const float *h, const float *drh, float *duq, float *duzr, float *dh, int act, int B,
+                                   int hc, int H, int W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,12 +79,21 @@ SIGNATURES = {
     "nlspn_gconv": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i,
                          ctypes.c_float, _i, _vp]),
     "nlspn_gconv_affnorm": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "nlspn_gconv_dgrad": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
+                               ctypes.c_float, _vp]),
+    "nlspn_gconv_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "nlspn_gconv_wgrad": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, ctypes.c_float, _vp, _i64, _i, _i, _i, _i,
+                               _i, _vp]),
+    "nlspn_gconv_gru_train": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
+                                   _vp]),
+    "nlspn_gconv_gru_gates_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 
 # Entry points an A/B build (NLSPN_LIB_PATH) of an earlier round may lack; any other
 # missing symbol fails the load (a stale or wrong library is refused up front)
 AB_OPTIONAL = frozenset({"nlspn_resident_status", "nlspn_resident_config", "nlspn_gconv_pack_layout", "nlspn_gconv",
-                         "nlspn_gconv_affnorm"})
+                         "nlspn_gconv_affnorm", "nlspn_gconv_dgrad", "nlspn_gconv_wgrad_workspace_bytes",
+                         "nlspn_gconv_wgrad", "nlspn_gconv_gru_train", "nlspn_gconv_gru_gates_backward"})
 
 _lib = None
 

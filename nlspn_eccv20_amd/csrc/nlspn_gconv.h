@@ -35,7 +35,9 @@ namespace nlspn {
 constexpr int kGcNT = 256;  // threads per workgroup (4 waves)
 constexpr int kGcCP = 16;   // packed input channels: a multiple of this (every chunk size CC divides it)
 enum { kGcS1 = 0, kGcS2 = 1, kGcT2 = 2 };         // 3x3 pad 1 stride 1 / stride 2; transposed stride 2 (pad 1, output pad 1)
-enum { kGcEpiAct = 0, kGcEpiGru1 = 1, kGcEpiGru2 = 2, kGcEpiAff = 3 };
+// kGcEpiDact: the data-gradient epilogue (nlspn_gconv_bwd.h): no bias; the sum times the
+// activation derivative of the saved forward output at the same element, times a scalar
+enum { kGcEpiAct = 0, kGcEpiGru1 = 1, kGcEpiGru2 = 2, kGcEpiAff = 3, kGcEpiDact = 4 };
 enum { kGcActNone = 0, kGcActRelu = 1, kGcActTanh = 2 };
 
 struct GconvArgs {
@@ -61,6 +63,16 @@ struct GconvArgs {
     // reference tap inserted, (B, K + 1, ohs, ows), of kind aff_kind (kAff*) with *gamma
     const float *gamma;
     int aff_kind;
+    // training forward of the ConvGRU (optional, null at inference): GRU1 also stores r, GRU2 q
+    float *rb, *qb;
+    // kGcEpiDact: y (channels [0, ysplit)) and y1 (channels [ysplit, cout)) = act'(ysave) * scale
+    // * sum (+ add / add1, laid out as y / y1; they may be y / y1 themselves).  ysave: the layer
+    // output whose pre-activation gradient this is, laid out as y (ysplit = cout then);
+    // act: its activation.
+    const float *ysave, *add, *add1;
+    float *y1;
+    int ysplit;
+    float scale;
 };
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
@@ -280,7 +292,10 @@ __device__ __forceinline__ void gconv_body(const GconvArgs &a, float *lds, int w
 #pragma unroll
     for (int m = 0; m < WM; ++m)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) bv[m][r] = a.bias[co0 + 16 * m + 4 * lg + r];  // (padded to the co tiles)
+        for (int r = 0; r < 4; ++r) {
+            if constexpr (EPI == kGcEpiDact) bv[m][r] = 0.f;  // (a gradient carries no bias)
+            else bv[m][r] = a.bias[co0 + 16 * m + 4 * lg + r];  // (padded to the co tiles)
+        }
     const int hc = a.hc;
     const int gate = EPI == kGcEpiGru1 ? (cot * WGCO) / hc : 0;  // GRU1: 0 z, 1 r, 2 qx (uniform per tile)
 #pragma unroll
@@ -323,8 +338,11 @@ __device__ __forceinline__ void gconv_body(const GconvArgs &a, float *lds, int w
                     const float u = acc[m][n][r] + bv[m][r];
                     float o;
                     if (gate == 0) o = 1.f / (1.f + expf(-u));                    // z
-                    else if (gate == 1) o = (1.f / (1.f + expf(-u))) * hv[m][r];  // r * h
-                    else o = u;                                                    // convq's x half + bias
+                    else if (gate == 1) {                                          // r * h
+                        const float rv = 1.f / (1.f + expf(-u));
+                        o = rv * hv[m][r];
+                        if (ok && a.rb) a.rb[ob + (long long)(16 * m + 4 * lg + r) * HWo] = rv;  // (training)
+                    } else o = u;                                                  // convq's x half + bias
                     if (ok) dst[ob + (long long)(16 * m + 4 * lg + r) * HWo] = o;
                 }
         } else if constexpr (EPI == kGcEpiAff) {
@@ -360,6 +378,27 @@ __device__ __forceinline__ void gconv_body(const GconvArgs &a, float *lds, int w
 #pragma unroll
                 for (int c = 5; c < 9; ++c) yb[c * HWs] = t[c - 1][0];
             }
+        } else if constexpr (EPI == kGcEpiDact) {
+            const long long pixs = ok ? (long long)oy * a.ows + ox : 0;
+            const long long HWs = (long long)a.ohs * a.ows;
+#pragma unroll
+            for (int m = 0; m < WM; ++m)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int co = co0 + 16 * m + 4 * lg + r;
+                    if (!ok || co >= a.cout) continue;
+                    const bool lo = co < a.ysplit;
+                    const long long o = lo ? ((long long)b * a.ysplit + co) * HWs + pixs
+                                           : ((long long)b * (a.cout - a.ysplit) + (co - a.ysplit)) * HWs + pixs;
+                    float u = acc[m][n][r] * a.scale;
+                    if (a.act != kGcActNone) {
+                        const float yv = a.ysave[o];
+                        u = a.act == kGcActRelu ? (yv > 0.f ? u : 0.f) : u * (1.f - yv * yv);
+                    }
+                    const float *ad = lo ? a.add : a.add1;
+                    if (ad) u += ad[o];
+                    (lo ? a.y : a.y1)[o] = u;
+                }
         } else {  // kGcEpiGru2
             float qv[WM][4], zv[WM][4], hv[WM][4];
             const long long ob = ((long long)b * hc + co0) * HWo + pix;
@@ -379,6 +418,7 @@ __device__ __forceinline__ void gconv_body(const GconvArgs &a, float *lds, int w
                     const float q = tanhf(acc[m][n][r] + qv[m][r]);
                     const float z = zv[m][r];
                     if (ok) a.hout[ob + (long long)(16 * m + 4 * lg + r) * HWo] = (1.f - z) * hv[m][r] + z * q;  // :402
+                    if (ok && a.qb) a.qb[ob + (long long)(16 * m + 4 * lg + r) * HWo] = q;  // (training)
                 }
         }
     }
@@ -502,5 +542,15 @@ __global__ void __launch_bounds__(kGsNT) gsmall_kernel(GconvArgs a, const float 
     X(23, kGcS2, 2, 1, 2, 2, 8, 40, 4, kGcEpiAct)                  \
     X(24, kGcS1, 2, 1, 2, 2, 6, 40, 8, kGcEpiGru2)                 \
     X(25, kGcT2, 1, 4, 1, 4, 6, 80, 8, kGcEpiAff)
+
+// The data-gradient presets NLSPN_GC_DG_* (nlspn_gconv_dgrad): the forward tilings of the adjoint
+// layer kind with the kGcEpiDact epilogue, and a stride-1 convolution with a plain epilogue (the
+// ConvGRU's adjoints).  Instantiated in nlspn_kern_gconv_bwd.hip.
+#define NLSPN_GC_DG_CONFIGS(X)                                     \
+    X(32, kGcT2, 4, 1, 1, 4, 6, 40, 8, kGcEpiDact)                 \
+    X(33, kGcT2, 1, 4, 1, 4, 6, 80, 8, kGcEpiDact)                 \
+    X(34, kGcS2, 4, 1, 1, 4, 12, 40, 4, kGcEpiDact)                \
+    X(35, kGcS2, 1, 1, 1, 4, 10, 72, 8, kGcEpiDact)                \
+    X(36, kGcS1, 2, 2, 2, 2, 8, 40, 8, kGcEpiDact)
 
 }  // namespace nlspn

@@ -17,9 +17,24 @@ VALU kernel (as MFMA tiles their K would be mostly padding).  Numerics: exact f3
 accumulation; only the summation order differs from MIOpen's (RMSE vs the reference's
 GRU-mode fixtures well inside their 1e-4 bar, tests/test_gpu_gru.py).
 
-Inference only (no autograd formula): NLSPNModel uses it when gradients are off; training
-keeps the torch modules.  Weights are packed once per weight version into the kernels'
-layout and cached (``GruConvs.pack``).
+Training runs on the same kernels.  With gradients enabled every layer chain and the ConvGRU
+cell is a ``torch.autograd.Function`` (``_ChainFn``, ``_GruFn``) taking the modules' own
+``weight`` / ``bias`` parameters, whose backward issues (``csrc/nlspn_gconv_bwd.h``):
+  * data gradients as forward launches of the ADJOINT layer kind on adjoint-packed weights
+    (a stride-2 conv's adjoint is the transposed conv of the same tensor and vice versa; a
+    stride-1 conv's is the conv with flipped taps and transposed channels), whose epilogue
+    multiplies by the activation derivative of the layer below (from its saved output), so
+    every launch hands the next one a pre-activation gradient;
+  * weight / bias gradients as an MFMA implicit GEMM over pixels, split over workgroups into
+    f32 slabs that a second launch sums in a fixed order (no atomics: bit-reproducible);
+  * the ConvGRU's gate derivatives as two pointwise launches around the candidate's data
+    gradient; the training forward is the inference launches plus stores of r and q.
+The forward values are those of the inference launches, bit for bit.  Under gradients
+``decode_aff`` returns the raw taps (the differentiable ``affinity_normalization`` follows).
+
+Weights are packed once per weight version into the kernels' layout and cached
+(``GruConvs.pack``), the adjoint packs beside the forward ones on the first call under
+gradients.  ``GruConvs.stats`` counts the launches per kind.
 """
 from __future__ import annotations
 
@@ -30,9 +45,11 @@ import torch.nn as nn
 
 from . import _lib
 
-__all__ = ["GruConvs", "GC_S2", "GC_S2_C16", "GC_GRU1", "GC_GRU2", "GC_T2", "GC_T2_C16", "GC_S2_SMALL"]
+__all__ = ["GruConvs", "pack_adjoint", "pack_adjoint_s1", "unpack_conv", "unpack_convt", "GC_S2", "GC_S2_C16", "GC_GRU1", "GC_GRU2", "GC_T2", "GC_T2_C16", "GC_S2_SMALL"]
 
 GC_S2, GC_S2_C16, GC_GRU1, GC_GRU2, GC_T2, GC_T2_C16, GC_S2_SMALL = range(7)
+# the data-gradient presets (NLSPN_GC_DG_*): the adjoint kind's tiling, derivative epilogue
+GC_DG_T2, GC_DG_T2_C16, GC_DG_S2, GC_DG_S2_C16, GC_DG_S1 = range(32, 37)
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 # the transposed conv's taps per output phase (py, px), in the kernel's order
 # (nlspn_gconv.h gc_tap): ky = 1 (py = 0) or 0, 2 (py = 1); likewise kx
@@ -93,10 +110,134 @@ def _has_relu(seq):
 
 
 class _Layer:
-    __slots__ = ("layer", "w", "b", "cin", "cout", "act")
+    # conv: the module (its parameters receive the gradients); adj / dg: the adjoint-packed
+    # weights and the data-gradient preset (training, GruConvs._pack_adjoints)
+    __slots__ = ("layer", "w", "b", "cin", "cout", "act", "conv", "adj", "dg")
 
-    def __init__(self, layer, w, b, cin, cout, act):
+    def __init__(self, layer, w, b, cin, cout, act, conv=None):
         self.layer, self.w, self.b, self.cin, self.cout, self.act = layer, w, b, cin, cout, act
+        self.conv, self.adj, self.dg = conv, None, None
+
+
+def pack_adjoint(conv):
+    """(preset, packed weights) of the data gradient of a stride-2 conv / transposed conv
+    module: the adjoint of a conv is the transposed conv of the same (Cout, Cin, 3, 3) tensor,
+    the adjoint of a transposed conv the conv reading its (Cin, Cout, 3, 3) tensor as (out, in)."""
+    if isinstance(conv, nn.ConvTranspose2d):
+        dg = GC_DG_S2_C16 if conv.in_channels <= 16 else GC_DG_S2
+        return dg, pack_conv(conv.weight, None, dg)[0]
+    dg = GC_DG_T2_C16 if conv.in_channels <= 16 else GC_DG_T2
+    return dg, pack_convt(conv.weight, None, dg)[0]
+
+
+def pack_adjoint_s1(weight):
+    """A stride-1 (Cout, Cin, 3, 3) conv's data gradient: the conv with the taps flipped and
+    the channels transposed, packed for GC_DG_S1."""
+    return pack_conv(weight.detach().transpose(0, 1).flip(2, 3), None, GC_DG_S1)[0]
+
+
+def unpack_conv(w, cout, cin, layer):
+    """Inverse of pack_conv: the (cout, cin, 3, 3) tensor of a packed conv weight."""
+    wgco, cc, _ = _layout(layer)
+    ct, cp = (cout + wgco - 1) // wgco, (cin + cc - 1) // cc * cc
+    return w.reshape(ct, cp, 9, wgco).permute(0, 3, 1, 2).reshape(ct * wgco, cp, 3, 3)[:cout, :cin]
+
+
+def unpack_convt(w, cin, cout, layer):
+    """Inverse of pack_convt: the (cin, cout, 3, 3) tensor of a packed transposed-conv weight."""
+    wgco, cc, _ = _layout(layer)
+    ct, cp = (cout + wgco - 1) // wgco, (cin + cc - 1) // cc * cc
+    out = torch.zeros((cin, cout, 3, 3), device=w.device, dtype=w.dtype)
+    o = 0
+    for taps in _T_TAPS:
+        n = ct * cp * len(taps) * wgco
+        part = w[o:o + n].reshape(ct, cp, len(taps), wgco).permute(0, 3, 1, 2).reshape(ct * wgco, cp, len(taps))
+        for t, (ky, kx) in enumerate(taps):
+            out[:, :, ky, kx] = part[:cout, :cin, t].t()
+        o += n
+    return out
+
+
+class _ChainFn(torch.autograd.Function):
+    """A chain of stride-2 convs or transposed convs (encode_dep, encode_aff, decode_aff; one
+    layer: that layer) on the HIP kernels, forward and backward.  params: weight, bias per layer."""
+
+    @staticmethod
+    def forward(ctx, gc, layers, in_div, crop, x, *params):
+        acts = [x.contiguous()]
+        for i, L in enumerate(layers):
+            if isinstance(L.conv, nn.ConvTranspose2d):
+                acts.append(gc._convt(L, acts[-1], crop=crop if i == len(layers) - 1 else None))
+            else:
+                acts.append(gc._conv_s2(L, acts[-1], in_div=in_div if i == 0 else 1.0))
+        ctx.gc, ctx.layers, ctx.in_div = gc, layers, in_div
+        ctx.save_for_backward(*acts)
+        return acts[-1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        gc, layers, acts = ctx.gc, ctx.layers, ctx.saved_tensors
+        g = g.contiguous()
+        if layers[-1].act != ACT_NONE:  # the chain's last activation (the layers below: in the dgrad epilogues)
+            g = gc._act_backward(g, acts[-1], layers[-1].act)
+        grads = []
+        for i in reversed(range(len(layers))):
+            L, xin = layers[i], acts[i]
+            scale = 1.0 / ctx.in_div if i == 0 else 1.0
+            grads[:0] = gc._wgrad(L, xin, g, scale)
+            if i > 0 or ctx.needs_input_grad[4]:
+                g = gc._dgrad(L, g, xin, layers[i - 1].act if i > 0 else ACT_NONE, scale)
+            else:
+                g = None
+        return (None, None, None, None, g, *grads)
+
+
+class _GruFn(torch.autograd.Function):
+    """The ConvGRU cell (nlspnmodel.py:398-403) on the HIP kernels, forward and backward."""
+
+    @staticmethod
+    def forward(ctx, gc, P, h, x, wz, bz, wr, br, wq, bq):
+        h, x = h.contiguous(), x.contiguous()
+        hc = P["hc"]
+        B, _, H, W = h.shape
+        z, r, rh, qx, q, hn = (torch.empty_like(h) for _ in range(6))
+        g1, g2 = P["gru1"], P["gru2"]
+        _lib.call("nlspn_gconv_gru_train", h.device, 1, h, x, x.shape[1], g1.w, g1.b, h, z, rh, qx, None, r, None,
+                  B, H, W, hc, _lib.STREAM)
+        _lib.call("nlspn_gconv_gru_train", h.device, 2, rh, None, 0, g2.w, g2.b, h, z, None, qx, hn, None, q,
+                  B, H, W, hc, _lib.STREAM)
+        gc.stats["fwd"] += 2
+        ctx.gc, ctx.P = gc, P
+        ctx.save_for_backward(h, x, z, r, q, rh)
+        return hn
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dhn):
+        gc, P = ctx.gc, ctx.P
+        h, x, z, r, q, rh = ctx.saved_tensors
+        hc = P["hc"]
+        B, _, H, W = h.shape
+        dev = h.device
+        dhn = dhn.contiguous()
+        duq, drh, dh, dx = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h), torch.empty_like(x)
+        duzr = torch.empty((B, 2 * hc, H, W), device=dev, dtype=torch.float32)
+        _lib.call("nlspn_gconv_gru_gates_backward", dev, 1, dhn, z, None, q, h, None, duq, duzr, None, 0, B, hc, H, W,
+                  _lib.STREAM)
+        # convq's adjoint: d(r h) and its share of dx
+        _lib.call("nlspn_gconv_dgrad", dev, GC_DG_S1, duq, hc, P["adj_q"], None, None, None, drh, dx, hc, B, H, W,
+                  hc + x.shape[1], H, W, ACT_NONE, 1.0, _lib.STREAM)
+        _lib.call("nlspn_gconv_gru_gates_backward", dev, 2, dhn, z, r, None, h, drh, None, duzr, dh, 0, B, hc, H, W,
+                  _lib.STREAM)
+        # [convz; convr]'s adjoint, added into dh and dx in place
+        _lib.call("nlspn_gconv_dgrad", dev, GC_DG_S1, duzr, 2 * hc, P["adj_zr"], None, dh, dx, dh, dx, hc, B, H, W,
+                  hc + x.shape[1], H, W, ACT_NONE, 1.0, _lib.STREAM)
+        gc.stats["gates_bwd"] += 2
+        gc.stats["dgrad"] += 2
+        dwq, dbq = gc._wgrad_raw(1, duq, rh, x, False, 1.0)
+        dwzr, dbzr = gc._wgrad_raw(1, duzr, h, x, False, 1.0)
+        return None, None, dh, dx, dwzr[:hc], dbzr[:hc], dwzr[hc:], dbzr[hc:], dwq, dbq
 
 
 class GruConvs:
@@ -106,6 +247,14 @@ class GruConvs:
 
     def __init__(self):
         self._entries = {}
+        self._ws = {}  # (device, stream) -> the weight-gradient workspace
+        self.reset_stats()
+
+    def reset_stats(self):
+        """Launch counts per kind since the last reset: ``fwd`` (forward launches), ``dgrad``,
+        ``wgrad`` (kernel launches of the weight / bias gradients) and ``gates_bwd``; ``gru_fwd``
+        counts ConvGRU cell forwards."""
+        self.stats = {"fwd": 0, "dgrad": 0, "wgrad": 0, "gates_bwd": 0, "gru_fwd": 0}
 
     @staticmethod
     def supported(model) -> bool:
@@ -135,20 +284,31 @@ class GruConvs:
     def _raw(layer, conv, act):
         """A narrow layer for the VALU kernel: the module's own weight layout."""
         return _Layer(layer, conv.weight.detach().float().contiguous(), conv.bias.detach().float().contiguous(),
-                      conv.in_channels, conv.out_channels, act)
+                      conv.in_channels, conv.out_channels, act, conv)
+
+    @staticmethod
+    def _pack_adjoints(model, packed):
+        with torch.no_grad():
+            for L in packed["dep"] + packed["aff"] + packed["dec"]:
+                L.dg, L.adj = pack_adjoint(L.conv)
+            g = model.GRU
+            packed["adj_q"] = pack_adjoint_s1(g.convq.weight)
+            packed["adj_zr"] = pack_adjoint_s1(torch.cat([g.convz.weight, g.convr.weight], 0))
 
     def pack(self, model):
         params = [p for m in (model.encode_dep, model.encode_aff, model.GRU, model.decode_aff) for p in m.parameters()]
         key = (params[0].device, tuple((p.data_ptr(), p._version) for p in params))
         e = self._entries.get(params[0].device)
         if e is not None and e[0] == key:
+            if torch.is_grad_enabled() and "adj_q" not in e[1]:
+                self._pack_adjoints(model, e[1])
             return e[1]
         with torch.no_grad():
             enc = lambda seq: [_Layer(GC_S2_C16 if _conv_of(s).out_channels <= 16 else GC_S2,  # noqa: E731
                                       *pack_conv(_conv_of(s).weight, _conv_of(s).bias,
                                                  GC_S2_C16 if _conv_of(s).out_channels <= 16 else GC_S2),
                                       _conv_of(s).in_channels, _conv_of(s).out_channels,
-                                      ACT_RELU if _has_relu(s) else ACT_NONE) for s in seq]
+                                      ACT_RELU if _has_relu(s) else ACT_NONE, _conv_of(s)) for s in seq]
             dep = enc(list(model.encode_dep))
             aff = enc(list(model.encode_aff)[:3])
             # the first (1 / 9 -> 16 channel) convs on the VALU kernel
@@ -161,14 +321,17 @@ class GruConvs:
                           *pack_convt(_conv_of(s).weight, _conv_of(s).bias,
                                       GC_T2_C16 if _conv_of(s).out_channels <= 16 else GC_T2),
                           _conv_of(s).in_channels, _conv_of(s).out_channels,
-                          ACT_RELU if _has_relu(s) else ACT_NONE) for s in model.decode_aff]
+                          ACT_RELU if _has_relu(s) else ACT_NONE, _conv_of(s)) for s in model.decode_aff]
             g = model.GRU
             w1 = torch.cat([g.convz.weight, g.convr.weight, g.convq.weight], 0)
             b1 = torch.cat([g.convz.bias, g.convr.bias, g.convq.bias], 0)
             hc = g.convz.out_channels
             gru1 = _Layer(GC_GRU1, *pack_conv(w1, b1, GC_GRU1), 2 * hc, 3 * hc, ACT_NONE)
             gru2 = _Layer(GC_GRU2, *pack_conv(g.convq.weight[:, :hc], g.convq.bias, GC_GRU2), hc, hc, ACT_NONE)
-        packed = {"dep": dep, "aff": aff, "dec": dec, "gru1": gru1, "gru2": gru2, "hc": hc}
+        packed = {"dep": dep, "aff": aff, "dec": dec, "gru1": gru1, "gru2": gru2, "hc": hc,
+                  "gru_params": [g.convz.weight, g.convz.bias, g.convr.weight, g.convr.bias, g.convq.weight, g.convq.bias]}
+        if torch.is_grad_enabled():
+            self._pack_adjoints(model, packed)
         self._entries[params[0].device] = (key, packed)
         return packed
 
@@ -185,6 +348,7 @@ class GruConvs:
         Ho, Wo = (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1
         y = torch.empty((B, L.cout, Ho, Wo), device=x.device, dtype=torch.float32)
         self._run(L, x, L.cin, out=y, ohs=Ho, ows=Wo, in_div=in_div)
+        self.stats["fwd"] += 1
         return y
 
     def _convt(self, L, x, crop=None):
@@ -193,16 +357,21 @@ class GruConvs:
         ohs, ows = (min(crop[0], Ho), min(crop[1], Wo)) if crop else (Ho, Wo)
         y = torch.empty((B, L.cout, ohs, ows), device=x.device, dtype=torch.float32)
         self._run(L, x, L.cin, out=y, ohs=ohs, ows=ows)
+        self.stats["fwd"] += 1
         return y
 
     def encode_dep(self, P, new_pred, max_depth):
         """encode_dep(new_pred / max_depth) (:366): the division in the first conv's loads."""
+        if torch.is_grad_enabled():
+            return self._chain(P["dep"], new_pred, in_div=float(max_depth))
         x = new_pred.contiguous().float()
         for i, L in enumerate(P["dep"]):
             x = self._conv_s2(L, x, in_div=float(max_depth) if i == 0 else 1.0)
         return x
 
     def encode_aff(self, P, aff):
+        if torch.is_grad_enabled():
+            return self._chain(P["aff"], aff)
         x = aff.contiguous().float()
         for L in P["aff"]:
             x = self._conv_s2(L, x)
@@ -210,12 +379,16 @@ class GruConvs:
 
     def gru(self, P, h, x):
         """ConvGRU (:398-403): h' = (1 - z) h + z q."""
+        self.stats["gru_fwd"] += 1
+        if torch.is_grad_enabled():
+            return _GruFn.apply(self, P, h, x, *P["gru_params"])
         h, x = h.contiguous(), x.contiguous()
         hc = P["hc"]
         z, rh, qx = (torch.empty_like(h) for _ in range(3))
         hn = torch.empty_like(h)
         self._run(P["gru1"], h, hc, x, x.shape[1], h=h, zb=z, rhb=rh, qxb=qx, hc=hc)
         self._run(P["gru2"], rh, hc, h=h, zb=z, qxb=qx, hout=hn, hc=hc)
+        self.stats["fwd"] += 2
         return hn
 
     def decode_aff(self, P, h, crop, gamma=None, kind=None):
@@ -224,7 +397,10 @@ class GruConvs:
         (_affinity_normalization + _aff_insert, :179-201, :261-269) in its epilogue
         (nlspn_gconv_affnorm): the (B, K+1, H, W) affinity, bit-equal to the conv followed by
         ``affinity_normalization``, without the raw planes' round trip or a launch.  Otherwise
-        the raw (B, K, H, W) taps."""
+        the raw (B, K, H, W) taps (always under gradients: the differentiable
+        ``affinity_normalization`` follows)."""
+        if torch.is_grad_enabled():
+            return self._chain(P["dec"], h, crop=crop)
         x = h
         for L in P["dec"][:-1]:
             x = self._convt(L, x)
@@ -237,4 +413,66 @@ class GruConvs:
         y = torch.empty((B, L.cout + 1, ohs, ows), device=x.device, dtype=torch.float32)
         _lib.call("nlspn_gconv_affnorm", x.device, x, L.cin, L.w, L.b, y, g, _lib.AFF_KINDS[kind],
                   B, Hi, Wi, L.cout, ohs, ows, L.act, _lib.STREAM)
+        self.stats["fwd"] += 1
         return y
+
+    # ------------------------------------------------------------------ training
+    def _chain(self, layers, x, in_div=1.0, crop=None):
+        """The layers on the HIP kernels under autograd (_ChainFn): the modules' parameters receive dW / db."""
+        params = [p for L in layers for p in (L.conv.weight, L.conv.bias)]
+        return _ChainFn.apply(self, layers, in_div, crop, x.float(), *params)
+
+    def layer(self, conv, x, act=ACT_NONE, in_div=1.0, crop=None):
+        """One stride-2 conv / transposed conv module with activation ``act`` on the HIP kernels,
+        differentiable: a one-layer chain packed on the spot (tests; the model uses the cached packs)."""
+        with torch.no_grad():
+            if isinstance(conv, nn.ConvTranspose2d):
+                kind = GC_T2_C16 if conv.out_channels <= 16 else GC_T2
+                L = _Layer(kind, *pack_convt(conv.weight, conv.bias, kind), conv.in_channels, conv.out_channels, act, conv)
+            elif conv.out_channels == 16 and conv.in_channels <= 16:
+                L = self._raw(GC_S2_SMALL, conv, act)
+            else:
+                kind = GC_S2_C16 if conv.out_channels <= 16 else GC_S2
+                L = _Layer(kind, *pack_conv(conv.weight, conv.bias, kind), conv.in_channels, conv.out_channels, act, conv)
+            L.dg, L.adj = pack_adjoint(conv)
+        return self._chain([L], x, in_div=in_div, crop=crop)
+
+    def _act_backward(self, g, y, act):
+        out = torch.empty_like(g)
+        _lib.call("nlspn_gconv_gru_gates_backward", g.device, 0, g, y, None, None, None, None, out, None, None, act,
+                  1, 1, 1, g.numel(), _lib.STREAM)
+        self.stats["dgrad"] += 1
+        return out
+
+    def _dgrad(self, L, g, xin, act_below, scale):
+        """dL/d(pre-activation of the layer below) = act_below'(xin) * scale * adjoint(L)(g)."""
+        B, cg, Hg, Wg = g.shape
+        dx = torch.empty_like(xin)
+        _, cout, Ho, Wo = xin.shape
+        _lib.call("nlspn_gconv_dgrad", g.device, L.dg, g, cg, L.adj, xin if act_below != ACT_NONE else None, None,
+                  None, dx, None, cout, B, Hg, Wg, cout, Ho, Wo, act_below, scale, _lib.STREAM)
+        self.stats["dgrad"] += 1
+        return dx
+
+    def _wgrad(self, L, xin, g, scale):
+        if isinstance(L.conv, nn.ConvTranspose2d):  # small = the input, large = the (cropped) output gradient
+            return self._wgrad_raw(2, xin, g, None, True, scale)
+        return self._wgrad_raw(2, g, xin, None, False, scale)
+
+    def _wgrad_raw(self, stride, s, l0, l1, bias_from_large, scale):
+        """(dW (Cs, Cl, 3, 3), db) of nlspn_gconv_wgrad: s the small tensor, l0 (+ l1) the large one."""
+        lib = _lib.get()
+        B, Cs, Hs, Ws = s.shape
+        c0, c1 = l0.shape[1], 0 if l1 is None else l1.shape[1]
+        Hl, Wl = l0.shape[2:]
+        need = lib.nlspn_gconv_wgrad_workspace_bytes(stride, Cs, c0 + c1, B, Hs, Ws, Hl, Wl)
+        key = (s.device, torch.cuda.current_stream(s.device).cuda_stream)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() * 4 < need:
+            ws = self._ws[key] = torch.empty((need + 3) // 4, device=s.device, dtype=torch.float32)
+        dw = torch.empty((Cs, c0 + c1, 3, 3), device=s.device, dtype=torch.float32)
+        db = torch.empty(c0 if bias_from_large else Cs, device=s.device, dtype=torch.float32)
+        _lib.call("nlspn_gconv_wgrad", s.device, stride, s, Cs, l0, c0, l1, c1, dw, db, int(bias_from_large), scale,
+                  ws, ws.numel() * 4, B, Hs, Ws, Hl, Wl, _lib.STREAM)
+        self.stats["wgrad"] += 4
+        return dw, db

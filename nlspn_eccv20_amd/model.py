@@ -248,9 +248,12 @@ class NLSPNModel(nn.Module):
         if args.use_S2D:
             self.S2D = S2D()
         self._head_weights = HeadWeights()  # packed head-epilogue weights (a cache, not state)
-        # GRU mode at inference: encode_dep / encode_aff / ConvGRU / decode_aff as HIP
-        # convolutions (gru.py); False keeps the torch modules (A/B, tests)
+        # GRU mode: encode_dep / encode_aff / ConvGRU / decode_aff as HIP convolutions (gru.py),
+        # at inference and, with native_gru_train, under gradients (their HIP backward:
+        # nlspn_gconv_bwd.h; off by default: slower than the tuned modules);
+        # native_gru = False keeps the torch modules everywhere (A/B, tests)
         self.native_gru = True
+        self.native_gru_train = False
         self._gru_convs = GruConvs()
         params = nn.ParameterList([p for p in self.parameters() if p.requires_grad])
         self.param_groups = [{"params": params, "lr": args.lr}]
@@ -420,10 +423,13 @@ class NLSPNModel(nn.Module):
                 "gamma": self.aff_scale_const.data, "confidence": conf_eff}
 
     def _native_gru(self, x):
-        """The GRU-mode convolutions run on the HIP kernels (gru.py): inference on CUDA with the
-        reference's GRU architecture; training keeps the torch modules (their autograd)."""
-        return (self.native_gru and x.is_cuda and not torch.is_grad_enabled() and x.dtype == torch.float32
-                and GruConvs.supported(self))
+        """The GRU-mode convolutions run on the HIP kernels (gru.py): on CUDA with the reference's
+        GRU architecture, at inference and (native_gru_train) under gradients, where their
+        autograd Functions route dW / db to the modules' parameters.  A DataParallel replica keeps
+        the torch modules under gradients (its parameters are broadcast copies, see _head_cache)."""
+        if torch.is_grad_enabled() and (not self.native_gru_train or getattr(self, "_is_replica", False)):
+            return False
+        return self.native_gru and x.is_cuda and x.dtype == torch.float32 and GruConvs.supported(self)
 
     def _gru_update(self, aff_feat, aff, new_pred, k):
         """nlspnmodel.py:365-371: encode the new depth, (at the first update) encode the
