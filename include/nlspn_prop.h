@@ -394,7 +394,8 @@ int nlspn_resident_status(int clear);
  *   decode_aff + _clip_as     (:140-143, :228-250)  NLSPN_GC_T2 / NLSPN_GC_T2_C16: 3x3
  *                                          transposed stride 2 pad 1 output pad 1
  * x0 (c0 channels) then x1 (c1 channels, may be null with c1 = 0) are the input channels
- * (torch.cat order, read in place); Hi x Wi the input size.  wpk: the weights packed by
+ * (torch.cat order, read in place; with c1 > 0, c0 must be a multiple of 16: a chunk of
+ * input channels is staged from one source, else NLSPN_EINVAL); Hi x Wi the input size.  wpk: the weights packed by
  * nlspn_gconv_pack_layout's layout (nlspn_eccv20_amd/gru.py packs them), bias padded to
  * the co tiles.  NLSPN_GC_S2* / NLSPN_GC_T2*: y = act(conv + bias) stored as (B, cout, ohs,
  * ows) (ohs / ows <= the full output size: the crop), act NLSPN_GC_ACT_*, inputs divided by

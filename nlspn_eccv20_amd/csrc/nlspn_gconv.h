@@ -29,16 +29,9 @@
 #pragma once
 
 #include "nlspn_common.h"
+#include "nlspn_gconv_plan.h"
 
 namespace nlspn {
-
-constexpr int kGcNT = 256;  // threads per workgroup (4 waves)
-constexpr int kGcCP = 16;   // packed input channels: a multiple of this (every chunk size CC divides it)
-enum { kGcS1 = 0, kGcS2 = 1, kGcT2 = 2 };         // 3x3 pad 1 stride 1 / stride 2; transposed stride 2 (pad 1, output pad 1)
-// kGcEpiDact: the data-gradient epilogue (nlspn_gconv_bwd.h): no bias; the sum times the
-// activation derivative of the saved forward output at the same element, times a scalar
-enum { kGcEpiAct = 0, kGcEpiGru1 = 1, kGcEpiGru2 = 2, kGcEpiAff = 3, kGcEpiDact = 4 };
-enum { kGcActNone = 0, kGcActRelu = 1, kGcActTanh = 2 };
 
 struct GconvArgs {
     const float *x0, *x1;  // inputs (B, c0, Hi, Wi) and (B, c1, Hi, Wi): channels [0, c0) and [c0, c0 + c1)
@@ -110,7 +103,8 @@ __host__ __device__ constexpr int gc_round(int v, int m) { return (v + m - 1) / 
 
 template <int MODE, int WM, int WN, int WGM, int WGN, int XR, int XP, int CC, int EPI>
 struct GcCfg {
-    static constexpr int WGCO = 16 * WM * WGM, NPX = 16 * WN * WGN;
+    using Geom = GcGeom<MODE, WM, WN, WGM, WGN, XR, XP>;  // (nlspn_gconv_plan.h)
+    static constexpr int WGCO = Geom::WGCO, NPX = Geom::NPX;
     static constexpr int NTMAX = MODE == kGcT2 ? 4 : 9;
     static constexpr int XCS = gc_xcs(MODE, XR, XP);
     // One LDS stage = a chunk's weights [CC][WCS] then its input window [CC][XCS], each region
@@ -144,16 +138,12 @@ __device__ __forceinline__ void gconv_body(const GconvArgs &a, float *lds, int w
     rest /= a.tpb;
     const int band = rest % a.nbands;
     const int b = rest / a.nbands;
-    const int bx0 = band * a.bw, bwi = min(a.bw, a.gw - bx0);
     const int npx = a.npx;
-    const int f0 = tile * npx;
-    if (f0 >= a.gh * bwi) return;  // (the narrower last band has fewer tiles)
-    const int ra = f0 / bwi, rb = min(a.gh - 1, (f0 + npx - 1) / bwi);
-    // the window: input rows iy0 .. iy0 + nrows - 1, columns ix0 .. ix0 + ncols - 1
-    const int iy0 = MODE == kGcT2 ? ra : S * ra - 1;
-    const int ix0 = MODE == kGcT2 ? bx0 : S * bx0 - 1;
-    const int nrows = MODE == kGcT2 ? rb - ra + 2 : S * (rb - ra) + 3;
-    const int ncols = MODE == kGcT2 ? bwi + 1 : S * (bwi - 1) + 3;
+    // the tile's pixels and its window: input rows iy0 .. iy0 + nrows - 1, columns ix0 .. ix0 + ncols - 1
+    const GcWindow win = gc_window(MODE, a.gh, a.gw, a.bw, npx, band, tile);
+    if (win.empty) return;  // (the narrower last band has fewer tiles)
+    const int bx0 = win.bx0, bwi = win.bwi, f0 = win.f0, ra = win.ra, rb = win.rb;
+    const int iy0 = win.iy0, ix0 = win.ix0, nrows = win.nrows, ncols = win.ncols;
 
     // per n-block: this lane's pixel (grid row gy, column gx) and its window base
     int gyv[WN], gxv[WN], xb[WN];
@@ -424,33 +414,18 @@ __device__ __forceinline__ void gconv_body(const GconvArgs &a, float *lds, int w
     }
 }
 
-// GRU1's output-channel tiles differ in cost: z and r run K over h and x, qx over x alone (half).
-// One workgroup per (co tile, pixel tile) left the CUs unevenly loaded (every workgroup is
-// resident at once, so a CU's finish time is its summed work: 3.5 heavy-tile units on the most
-// loaded CUs against 2.8 on average).  A qx workgroup takes TWO consecutive pixel tiles instead,
-// so every workgroup costs the same.  (The pixel tiles of a GRU1 launch: gc_rest_count.)
-__host__ __device__ inline int gc_gru1_heavy_cots(const GconvArgs &a, int wgco) { return (2 * a.hc) / wgco; }
-__host__ __device__ inline int gc_rest_count(const GconvArgs &a) { return a.B * a.nbands * a.tpb; }
-__host__ __device__ inline int gc_gru1_wgs(const GconvArgs &a, int wgco) {
-    const int nh = gc_gru1_heavy_cots(a, wgco), nr = gc_rest_count(a);
-    return nh * nr + (a.co_tiles - nh) * ((nr + 1) / 2);
-}
-
 template <int MODE, int WM, int WN, int WGM, int WGN, int XR, int XP, int CC, int EPI>
 __global__ void __launch_bounds__(kGcNT) gconv_kernel(GconvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float gc_lds[];
     if constexpr (EPI == kGcEpiGru1) {
         using Cfg = GcCfg<MODE, WM, WN, WGM, WGN, XR, XP, CC, EPI>;
-        const int nh = gc_gru1_heavy_cots(a, Cfg::WGCO), nr = gc_rest_count(a);
-        const int wg = xcd_remap((int)blockIdx.x, gc_gru1_wgs(a, Cfg::WGCO));
-        if (wg < nh * nr) {  // z / r: one pixel tile
-            gconv_body<MODE, WM, WN, WGM, WGN, XR, XP, CC, EPI, 0>(a, gc_lds, wg % nh + (wg / nh) * a.co_tiles);
-        } else {             // qx: two pixel tiles in turn
-            const int w = wg - nh * nr, nl = a.co_tiles - nh;
-            const int cot = nh + w % nl, r0 = 2 * (w / nl);
-            gconv_body<MODE, WM, WN, WGM, WGN, XR, XP, CC, EPI, 0>(a, gc_lds, cot + r0 * a.co_tiles);
-            if (r0 + 1 < nr) gconv_body<MODE, WM, WN, WGM, WGN, XR, XP, CC, EPI, 0>(a, gc_lds, cot + (r0 + 1) * a.co_tiles);
-        }
+        // (a qx workgroup takes two pixel tiles: gc_gru1_map, nlspn_gconv_plan.h)
+        const int nh = gc_gru1_heavy_cots(a.hc, Cfg::WGCO), nr = gc_rest_count(a.B, a.nbands, a.tpb);
+        const int wg = xcd_remap((int)blockIdx.x, gc_gru1_wgs(a.hc, Cfg::WGCO, a.co_tiles, nr));
+        int cot, r0, r1;
+        gc_gru1_map(wg, nh, nr, a.co_tiles, cot, r0, r1);
+        gconv_body<MODE, WM, WN, WGM, WGN, XR, XP, CC, EPI, 0>(a, gc_lds, cot + r0 * a.co_tiles);
+        if (r1 >= 0) gconv_body<MODE, WM, WN, WGM, WGN, XR, XP, CC, EPI, 0>(a, gc_lds, cot + r1 * a.co_tiles);
         return;
     }
     const int per_phase = a.co_tiles * a.B * a.nbands * a.tpb;
@@ -519,38 +494,6 @@ __global__ void __launch_bounds__(kGsNT) gsmall_kernel(GconvArgs a, const float 
     }
 }
 
-// The instantiated configurations: X(id, MODE, WM, WN, WGM, WGN, XR, XP, CC, EPI).  Ids 0..5, 23 and 24
-// are the presets NLSPN_GC_* of include/nlspn_prop.h (23 / 24: NLSPN_GC_S2 / NLSPN_GC_GRU2 on
-// 32-pixel tiles, which nlspn_gconv picks for small grids; 25: NLSPN_GC_T2_C16 with the affinity
-// normalisation in its epilogue, nlspn_gconv_affnorm); the other ids >= 16 are alternative tilings of the same
-// layer kinds, selectable through nlspn_gconv's layer argument for A/B timing
-// (tools/gc_bench.py) and bit-compatible with the preset of their kind in layout (the packed
-// weights depend only on the kind's output-channel tile, which a variant must keep).
-#define NLSPN_GC_CONFIGS(X)                                        \
-    X(0, kGcS2, 4, 1, 1, 4, 12, 40, 4, kGcEpiAct)                  \
-    X(1, kGcS2, 1, 1, 1, 4, 10, 72, 8, kGcEpiAct)                  \
-    X(2, kGcS1, 2, 2, 2, 2, 6, 40, 4, kGcEpiGru1)                  \
-    X(3, kGcS1, 2, 2, 2, 2, 8, 40, 8, kGcEpiGru2)                  \
-    X(4, kGcT2, 4, 1, 1, 4, 6, 40, 8, kGcEpiAct)                   \
-    X(5, kGcT2, 1, 4, 1, 4, 6, 80, 8, kGcEpiAct)                   \
-    X(16, kGcS1, 2, 2, 2, 2, 8, 40, 8, kGcEpiGru1)                 \
-    X(17, kGcS1, 2, 2, 2, 2, 6, 40, 4, kGcEpiGru2)                 \
-    X(18, kGcS1, 2, 4, 2, 2, 8, 40, 8, kGcEpiGru1)                 \
-    X(20, kGcS2, 4, 1, 1, 4, 12, 40, 8, kGcEpiAct)                 \
-    X(21, kGcT2, 4, 1, 1, 4, 6, 40, 4, kGcEpiAct)                  \
-    X(22, kGcT2, 1, 4, 1, 4, 6, 80, 4, kGcEpiAct)                  \
-    X(23, kGcS2, 2, 1, 2, 2, 8, 40, 4, kGcEpiAct)                  \
-    X(24, kGcS1, 2, 1, 2, 2, 6, 40, 8, kGcEpiGru2)                 \
-    X(25, kGcT2, 1, 4, 1, 4, 6, 80, 8, kGcEpiAff)
-
-// The data-gradient presets NLSPN_GC_DG_* (nlspn_gconv_dgrad): the forward tilings of the adjoint
-// layer kind with the kGcEpiDact epilogue, and a stride-1 convolution with a plain epilogue (the
-// ConvGRU's adjoints).  Instantiated in nlspn_kern_gconv_bwd.hip.
-#define NLSPN_GC_DG_CONFIGS(X)                                     \
-    X(32, kGcT2, 4, 1, 1, 4, 6, 40, 8, kGcEpiDact)                 \
-    X(33, kGcT2, 1, 4, 1, 4, 6, 80, 8, kGcEpiDact)                 \
-    X(34, kGcS2, 4, 1, 1, 4, 12, 40, 4, kGcEpiDact)                \
-    X(35, kGcS2, 1, 1, 1, 4, 10, 72, 8, kGcEpiDact)                \
-    X(36, kGcS1, 2, 2, 2, 2, 8, 40, 8, kGcEpiDact)
+// (the instantiated configurations NLSPN_GC_CONFIGS / NLSPN_GC_DG_CONFIGS: nlspn_gconv_plan.h)
 
 }  // namespace nlspn

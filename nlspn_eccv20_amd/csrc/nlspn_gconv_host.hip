@@ -59,24 +59,14 @@ int nlspn_gconv_pack_layout(int layer, int *co_tile, int *cin_chunk, int *transp
 }  // extern "C"
 namespace {
 // the pixel tiling of a launch (a.Hi / a.Wi / a.Ho / a.Wo set): column bands and tiles per band
+// (gc_tile, nlspn_gconv_plan.h)
 int gc_tile(const GcPreset &p, GconvArgs &a) {
-    a.gh = p.mode == kGcT2 ? a.Hi : a.Ho;
-    a.gw = p.mode == kGcT2 ? a.Wi : a.Wo;
-    // column bands: the window's columns within the LDS pitch
-    const int bwmax = p.mode == kGcS1 ? p.xp - 2 : p.mode == kGcS2 ? (p.xp - 3) / 2 + 1 : p.xp - 1;
-    a.nbands = (a.gw + bwmax - 1) / bwmax;
-    a.bw = (a.gw + a.nbands - 1) / a.nbands;
-    // the rows a tile of npx pixels spans (at most (npx + bw - 2) / bw row steps), within the
-    // window's XR rows: narrow bands take fewer pixels per tile
-    const auto rows_of = [&](int npx) {
-        const int dr = (npx + a.bw - 2) / a.bw;
-        return p.mode == kGcS1 ? dr + 3 : p.mode == kGcS2 ? 2 * dr + 3 : dr + 2;
-    };
-    a.npx = p.npx;
-    while (a.npx > 1 && rows_of(a.npx) > p.xr) --a.npx;
-    if (rows_of(a.npx) > p.xr)
+    GcTiling t;
+    const bool ok = nlspn::gc_tile(GcGeo{p.mode, p.wgco, p.npx, p.xr, p.xp}, p.mode == kGcT2 ? a.Hi : a.Ho,
+                                   p.mode == kGcT2 ? a.Wi : a.Wo, t);
+    a.gh = t.gh; a.gw = t.gw; a.bw = t.bw; a.nbands = t.nbands; a.tpb = t.tpb; a.npx = t.npx;
+    if (!ok)
         return fail(NLSPN_EUNSUPPORTED, "gconv: a tile of a %d-wide band spans more than %d window rows", a.bw, p.xr);
-    a.tpb = (a.gh * a.bw + a.npx - 1) / a.npx;
     return NLSPN_OK;
 }
 
@@ -110,6 +100,11 @@ int gconv_impl(int layer, const float *x0, int c0, const float *x1, int c1, cons
     if (B < 1 || Hi < 1 || Wi < 1 || cout < 1 || c0 < 1 || c1 < 0 || (c1 > 0 && !x1))
         return fail(NLSPN_EINVAL, "gconv: bad shape B=%d Hi=%d Wi=%d c0=%d c1=%d cout=%d", B, Hi, Wi, c0, c1, cout);
     if (!x0 || !wpk || !bias) return fail(NLSPN_EINVAL, "gconv: null input, weights or bias");
+    // (a chunk of input channels is staged from one source: a chunk over x0's last channels
+    // would read zeros past them and the next one start past x1's first channels)
+    if (c1 > 0 && c0 % kGcCP != 0)
+        return fail(NLSPN_EINVAL, "gconv: a channel chunk would straddle the two sources (c0 = %d, not a multiple of %d)",
+                    c0, kGcCP);
     // (the MFMA kernels stage their inputs by LDS-DMA, untouched: a divided input is the VALU
     // kernel's, NLSPN_GC_S2_SMALL)
     if (in_div != 1.f) return fail(NLSPN_EINVAL, "gconv: in_div %g needs the NLSPN_GC_S2_SMALL preset", (double)in_div);
@@ -149,7 +144,7 @@ int gconv_impl(int layer, const float *x0, int c0, const float *x1, int c1, cons
     }
     NLSPN_TRY(gc_tile(p, a));
     long long nwg = (long long)(p.mode == kGcT2 ? 4 : 1) * a.co_tiles * B * a.nbands * a.tpb;
-    if (gru1) nwg = gc_gru1_wgs(a, p.wgco);  // (the qx workgroups take two pixel tiles each)
+    if (gru1) nwg = gc_gru1_wgs(a.hc, p.wgco, a.co_tiles, gc_rest_count(a.B, a.nbands, a.tpb));  // (the qx workgroups take two pixel tiles each)
     // Small grids: the same layer kind on 32-pixel tiles (the same co tile, hence the same packed
     // weights) when 64-pixel tiles would leave most CUs one workgroup (NYU B=8: the 1/8-scale last
     // encoder conv 104.1 -> 85.2 us, GRU2 52.6 -> 50.6 us; profiles/r06/gc_bench_layers_v4_n32.json)

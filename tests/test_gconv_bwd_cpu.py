@@ -90,6 +90,35 @@ def test_forward_entry_refuses_dgrad_presets():
     assert rc == _lib.EINVAL and "nlspn_gconv_dgrad" in lib.nlspn_last_error().decode()
 
 
+def _gconv(**over):
+    a = dict(layer=G.GC_S2, x0=P, c0=16, x1=P, c1=16, wpk=P, bias=P, y=P, h=None, zb=None, rhb=None, qxb=None, hout=None,
+             B=1, Hi=8, Wi=8, cout=64, ohs=4, ows=4, act=0, in_div=1.0, hc=0, stream=None)
+    a.update(over)
+    return _err(_lib.get().nlspn_gconv(*a.values()))
+
+
+@pytest.mark.parametrize("over", [
+    dict(c0=20, c1=12),                                   # a chunk of 4 or 8 channels over both sources
+    dict(c0=8, c1=8),
+    dict(layer=G.GC_T2, c0=24, c1=8, ohs=16, ows=16),
+    dict(layer=G.GC_GRU1, c0=120, c1=136, cout=384, hc=128, h=P, zb=P, rhb=P, qxb=P),
+])
+def test_forward_entry_refuses_a_split_that_straddles_a_chunk(over):
+    """Two sources whose first is no multiple of the 16 packed channels: a chunk over x0's last
+    channels would read zeros past them and x1's first channels would be skipped.  Refused
+    before any launch (the pointers are placeholders), as nlspn_gconv_wgrad refuses it."""
+    rc, text = _gconv(**over)
+    assert rc == _lib.EINVAL and "straddle" in text and f"c0 = {over['c0']}" in text, (rc, text)
+
+
+def test_forward_entry_validates_a_good_split_past_the_chunk_rule():
+    # the same call with c0 = 16 passes the channel rule: the next refusal is another one
+    rc, text = _gconv(c0=16, c1=16, ohs=9)
+    assert rc == _lib.EINVAL and "stored size" in text and "straddle" not in text, (rc, text)
+    rc, text = _gconv(c0=20, c1=0, x1=None, ohs=9)  # one source: any channel count
+    assert rc == _lib.EINVAL and "stored size" in text, (rc, text)
+
+
 def test_wgrad_workspace_is_a_pure_function_of_the_shape():
     lib = _lib.get()
     # GRU [convz; convr] at NYU B=8: 64 x 32 channel tiles -> 4 x 8 tiles, 512 / 32 = 16 K slices of

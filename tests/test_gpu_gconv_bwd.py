@@ -21,7 +21,11 @@ tests/test_backward_golden.py::test_gru_offset_matches_reference uses for GRU-mo
 Shapes (hidden width 128, the smallest supported): B=2 50x70 (every scale odd somewhere:
 25x35, 13x18, 7x9; decode_aff crops 56x72 -> 50x70; two column bands in the stride-2 layers)
 and B=1 24x320 (a 3x40 1/8-scale grid: two column bands and tiles spanning several rows in
-the stride-1 kernels)."""
+the stride-1 kernels); B=1 136x312, whose adjoint grids 34x78 and 17x39 split into uneven
+column bands (12 | 11 ... and 20 | 19): the narrower last band's tiles span one row more, which
+the planner once did not size the LDS window for (csrc/nlspn_gconv_plan.h gc_tile,
+tests/test_gconv_plan_cpu.py) — the data-gradient presets share the forward body and planner.
+The bars are unchanged by that shape."""
 import copy
 import functools
 import types
@@ -34,7 +38,7 @@ from nlspn_eccv20_amd.gru import ACT_NONE, ACT_RELU, ACT_TANH, GruConvs
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SHAPES = [(2, 50, 70), (1, 24, 320)]
+SHAPES = [(2, 50, 70), (1, 24, 320), (1, 136, 312)]
 CAP = 1e-4          # per layer / cell: the project's gradient bar, relative L2 against float64
 BARS = {"s2_relu": 2e-6, "s2_tanh": 3e-6, "small_dep": 9e-7, "small_aff": 7e-7, "t2_relu": 3e-6, "t2_c16_relu": 7e-7,
         "t2_last_crop": 8e-7, "gru": 3e-6}  # ~4x the measured native error (module docstring), all under CAP
