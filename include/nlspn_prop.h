@@ -501,6 +501,55 @@ int nlspn_gconv_gru_gates_backward(int stage, const float *dhn, const float *z, 
                                    const float *h, const float *drh, float *duq, float *duzr, float *dh, int act, int B,
                                    int hc, int H, int W, void *stream);
 
+/*
+ * GRU-mode convolutions on the f16 matrix cores, inference only, opt-in (csrc/nlspn_gconv16.h;
+ * NLSPNModel.gru_precision = "fp16").  The same layers as nlspn_gconv on
+ * v_mfma_f32_16x16x32_f16.  Numerics contract:
+ *   - MFMA operands are IEEE half: weights rounded to nearest-even once, when packed;
+ *     activations rounded once, in the epilogue of the layer that produces them (a plain
+ *     conversion: overflow gives inf, NaN is kept); no clamping anywhere;
+ *   - products are exact in f32 (11 + 11 significand bits), accumulation is f32 inside the MFMA;
+ *   - every epilogue (bias, ReLU, tanhf, sigmoid, the GRU blend) runs in f32 on the f32
+ *     accumulators, exactly as nlspn_gconv's;
+ *   - the ConvGRU state h is carried in f32 (every step also writes the f16 copy the next
+ *     convolutions read); z and qx stay f32; r*h is formed in f32 and stored as f16.
+ * Activation layout "c8": a (B, C, H, W) tensor as [B][ceil(C/8)][H][W][8] halves, pad channels
+ * zero (one window cell of eight channels = 16 bytes = one B fragment of the MFMA).  Weights:
+ * per co tile [ci/8][tap][co][8] halves (transposed: per output phase, the phases one after
+ * another), input channels padded to *cin_chunk (nlspn_gconv16_pack_layout; gru.py pack_conv16
+ * / pack_convt16); bias f32, padded to the co tiles.
+ *
+ * nlspn_gconv16(layer, ...): x0 (c0 channels) then x1 (c1 channels, null with c1 = 0) in c8
+ * (NLSPN_GC16_S2_SMALL: x0 f32 NCHW, wpk the module's own f32 (16, cin, 3, 3) tensor); with
+ * c1 > 0, c0 must be a multiple of the chunk (a chunk is staged from one source), else
+ * NLSPN_EINVAL.  Kinds:
+ *   NLSPN_GC16_S2_SMALL  1 / 9 -> 16 stride 2 on the VALU, nlspn_gconv's arithmetic (f32
+ *                        operands and sums, in_div); y16 only
+ *   NLSPN_GC16_S2        3x3 stride 2 pad 1; y16 (c8) and / or y32 (f32 NCHW), act
+ *   NLSPN_GC16_GRU1      x0 = h as c8, x1 = x, cout = 3 hc; reads h (f32); writes zb (f32),
+ *                        rh16 (c8), qxb (f32)
+ *   NLSPN_GC16_GRU2      x0 = rh16, cout = hc; reads h, zb, qxb (f32); writes hout32 (f32) and
+ *                        hout16 (c8), both required
+ *   NLSPN_GC16_T2 / NLSPN_GC16_T2_C16   transposed 3x3 stride 2 (64- / 16-channel co tile);
+ *                        y16 and / or y32, cropped to ohs x ows
+ * y16: (B, ceil(cout/8), ohs, ows, 8) halves; y32: (B, cout, ohs, ows) floats; either may be
+ * null, not both.  NLSPN_EINVAL before any device call for null required pointers, a preset
+ * that is not NLSPN_GC16_*, both outputs null, an output the kind does not write, in_div != 1
+ * outside NLSPN_GC16_S2_SMALL and a chunk that would straddle the two sources;
+ * NLSPN_EUNSUPPORTED for a grid no tile fits.
+ */
+#define NLSPN_GC16_S2 48
+#define NLSPN_GC16_GRU1 49
+#define NLSPN_GC16_GRU2 50
+#define NLSPN_GC16_T2 51
+#define NLSPN_GC16_T2_C16 52
+#define NLSPN_GC16_S2_SMALL 53
+int nlspn_gconv16_pack_layout(int layer, int *co_tile, int *cin_chunk, int *transposed);
+int nlspn_gconv16(int layer, const void *x0, int c0, const void *x1, int c1, const void *wpk, const float *bias,
+                  void *y16, float *y32, const float *h, float *zb, void *rh16, float *qxb, float *hout32,
+                  void *hout16, int B, int Hi, int Wi, int cout, int ohs, int ows, int act, float in_div, int hc,
+                  void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
 
 #include "nlspn_host.h"
 #include "nlspn_gconv_bwd.h"
+#include "nlspn_gconv16.h"
 
 namespace nlspn {
 // defined in nlspn_kern_gconv.hip
@@ -14,6 +15,10 @@ extern template __global__ void gsmall_kernel<16>(GconvArgs, const float *);
 NLSPN_GC_DG_CONFIGS(NLSPN_GC_EXTERN)
 #define NLSPN_GW_EXTERN(...) extern template __global__ void gwgrad_kernel<__VA_ARGS__>(GwgradArgs);
 NLSPN_GW_CONFIGS(NLSPN_GW_EXTERN)
+// defined in nlspn_kern_gconv16.hip
+#define NLSPN_GC16_EXTERN(id, ...) extern template __global__ void gconv16_kernel<__VA_ARGS__>(Gconv16Args);
+NLSPN_GC16_CONFIGS(NLSPN_GC16_EXTERN)
+extern template __global__ void gsmall16_kernel<16>(Gconv16Args, const float *);
 }  // namespace nlspn
 
 using namespace nlspn;
@@ -353,6 +358,121 @@ int nlspn_gconv_gru_gates_backward(int stage, const float *dhn, const float *z, 
     void *args[] = {&a, &stage};
     return launch_kernel(reinterpret_cast<const void *>(&ggates_kernel), dim3(elementwise_grid(a.n)), dim3(256), args, 0,
                          as_stream(stream), "nlspn_gconv_gru_gates_backward");
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- f16 operands (nlspn_gconv16.h)
+namespace {
+struct Gc16Preset {
+    const void *fn;
+    int mode, wgco, npx, xr, xp, ccb, lds, epi;
+};
+template <int MODE, int WM, int WN, int WGM, int WGN, int XR, int XP, int CCB, int EPI>
+Gc16Preset gc16_preset() {
+    using Cfg = Gc16Cfg<MODE, WM, WN, WGM, WGN, XR, XP, CCB, EPI>;
+    return Gc16Preset{reinterpret_cast<const void *>(&gconv16_kernel<MODE, WM, WN, WGM, WGN, XR, XP, CCB, EPI>), MODE,
+                      Cfg::WGCO, Cfg::NPX, XR, XP, CCB, Cfg::LDS_BYTES, EPI};
+}
+bool gc16_get(int layer, Gc16Preset &p) {
+    switch (layer) {
+#define NLSPN_GC16_CASE(id, ...) \
+    case id: p = gc16_preset<__VA_ARGS__>(); return true;
+        NLSPN_GC16_CONFIGS(NLSPN_GC16_CASE)
+        default: return false;
+    }
+}
+}  // namespace
+extern "C" {
+
+int nlspn_gconv16_pack_layout(int layer, int *co_tile, int *cin_chunk, int *transposed) {
+    if (layer == NLSPN_GC16_S2_SMALL) {  // the module's own f32 weight layout
+        if (co_tile) *co_tile = 0;
+        if (cin_chunk) *cin_chunk = 1;
+        if (transposed) *transposed = 0;
+        return NLSPN_OK;
+    }
+    Gc16Preset p;
+    if (!gc16_get(layer, p)) return fail(NLSPN_EINVAL, "gconv16: preset %d is not an f16 preset (NLSPN_GC16_*)", layer);
+    if (co_tile) *co_tile = p.wgco;
+    if (cin_chunk) *cin_chunk = 8 * p.ccb;
+    if (transposed) *transposed = p.mode == kGcT2;
+    return NLSPN_OK;
+}
+
+int nlspn_gconv16(int layer, const void *x0, int c0, const void *x1, int c1, const void *wpk, const float *bias,
+                  void *y16, float *y32, const float *h, float *zb, void *rh16, float *qxb, float *hout32,
+                  void *hout16, int B, int Hi, int Wi, int cout, int ohs, int ows, int act, float in_div, int hc,
+                  void *stream) {
+    Gc16Preset p{};
+    const bool small = layer == NLSPN_GC16_S2_SMALL;
+    if (!small && !gc16_get(layer, p))
+        return fail(NLSPN_EINVAL, "gconv16: preset %d is not an f16 preset (NLSPN_GC16_*)", layer);
+    if (B < 1 || Hi < 1 || Wi < 1 || cout < 1 || c0 < 1 || c1 < 0 || (c1 > 0 && !x1))
+        return fail(NLSPN_EINVAL, "gconv16: bad shape B=%d Hi=%d Wi=%d c0=%d c1=%d cout=%d", B, Hi, Wi, c0, c1, cout);
+    if (!x0 || !wpk || !bias) return fail(NLSPN_EINVAL, "gconv16: null input, weights or bias");
+    if (act < NLSPN_GC_ACT_NONE || act > NLSPN_GC_ACT_TANH) return fail(NLSPN_EINVAL, "gconv16: activation %d", act);
+    // (a chunk of channel blocks is staged from one source, through one descriptor)
+    if (!small && c1 > 0 && c0 % (8 * p.ccb) != 0)
+        return fail(NLSPN_EINVAL, "gconv16: a channel chunk would straddle the two sources (c0 = %d, not a multiple of %d)",
+                    c0, 8 * p.ccb);
+    if (!small && in_div != 1.f)
+        return fail(NLSPN_EINVAL, "gconv16: in_div %g needs the NLSPN_GC16_S2_SMALL preset", (double)in_div);
+    const bool gru = !small && (p.epi == kGcEpiGru1 || p.epi == kGcEpiGru2), gru1 = !small && p.epi == kGcEpiGru1;
+    Gconv16Args a{};
+    a.x0 = x0; a.x1 = x1; a.w = wpk; a.bias = bias;
+    a.y16 = static_cast<_Float16 *>(y16); a.y32 = y32;
+    a.h = h; a.zb = zb; a.rh16 = static_cast<_Float16 *>(rh16); a.qxb = qxb;
+    a.hout32 = hout32; a.hout16 = static_cast<_Float16 *>(hout16);
+    a.c0 = c0; a.c1 = c1; a.B = B; a.Hi = Hi; a.Wi = Wi; a.cout = cout; a.act = act; a.in_div = in_div; a.hc = hc;
+    if (small || p.mode == kGcS2) { a.Ho = (Hi - 1) / 2 + 1; a.Wo = (Wi - 1) / 2 + 1; }
+    else if (p.mode == kGcS1) { a.Ho = Hi; a.Wo = Wi; }
+    else { a.Ho = 2 * Hi; a.Wo = 2 * Wi; }
+    a.ohs = gru ? a.Ho : ohs;
+    a.ows = gru ? a.Wo : ows;
+    if (gru) {
+        if (y16 || y32) return fail(NLSPN_EINVAL, "gconv16: a GRU launch writes no y16 / y32 (output format not supported)");
+        if (hc < 1 || hc % p.wgco != 0 || !h || !zb || !qxb || c0 != hc ||
+            (gru1 ? (!rh16 || cout != 3 * hc) : (!hout32 || !hout16 || cout != hc || c1 != 0)))
+            return fail(NLSPN_EINVAL, "gconv16: GRU launch needs hc %% %d == 0, c0 = hc, h, z / qx, r*h (GRU1, cout 3hc) or "
+                        "both h' outputs (GRU2, cout hc)", p.wgco);
+    } else {
+        if (!y16 && !y32) return fail(NLSPN_EINVAL, "gconv16: both outputs null");
+        if (small && y32) return fail(NLSPN_EINVAL, "gconv16 small: the VALU kernel writes y16 only (output format not supported)");
+    }
+    if (a.ohs < 1 || a.ows < 1 || a.ohs > a.Ho || a.ows > a.Wo)
+        return fail(NLSPN_EINVAL, "gconv16: stored size %dx%d outside the output %dx%d", a.ohs, a.ows, a.Ho, a.Wo);
+    if (small) {
+        if (c1 != 0 || cout != 16 || c0 * 16 * 9 > kGsMaxW)
+            return fail(NLSPN_EINVAL, "gconv16 small: cin %d (c1 %d), cout %d outside the VALU kernel's range (cout 16, "
+                        "cin <= 16)", c0, c1, cout);
+        const long long npix = (long long)B * a.ohs * a.ows;
+        const unsigned grid = (unsigned)std::min<long long>((npix + kGsNT - 1) / kGsNT, 1 << 20);
+        const float *wf = static_cast<const float *>(wpk);
+        void *args[] = {&a, &wf};
+        return launch_kernel(reinterpret_cast<const void *>(&gsmall16_kernel<16>), dim3(grid), dim3(kGsNT), args, 0,
+                             as_stream(stream), "nlspn_gconv16 small");
+    }
+    a.nb0 = (c0 + 7) / 8;
+    a.nb1 = (c1 + 7) / 8;
+    a.nbp = (a.nb0 + a.nb1 + p.ccb - 1) / p.ccb * p.ccb;
+    a.co_tiles = (cout + p.wgco - 1) / p.wgco;
+    {
+        GcTiling t;
+        const bool ok = nlspn::gc_tile(GcGeo{p.mode, p.wgco, p.npx, p.xr, p.xp}, p.mode == kGcT2 ? Hi : a.Ho,
+                                       p.mode == kGcT2 ? Wi : a.Wo, t);
+        a.gh = t.gh; a.gw = t.gw; a.bw = t.bw; a.nbands = t.nbands; a.tpb = t.tpb; a.npx = t.npx;
+        if (!ok)
+            return fail(NLSPN_EUNSUPPORTED, "gconv16: a tile of a %d-wide band spans more than %d window rows", a.bw, p.xr);
+    }
+    long long nwg = (long long)(p.mode == kGcT2 ? 4 : 1) * a.co_tiles * B * a.nbands * a.tpb;
+    if (gru1) nwg = gc_gru1_wgs(a.hc, p.wgco, a.co_tiles, gc_rest_count(a.B, a.nbands, a.tpb));
+    // (one image's channel blocks of a source within a 32-bit buffer descriptor)
+    if (nwg > 0x7fffffffLL || (long long)std::max(a.nb0, a.nb1) * Hi * Wi * 16 > 0x7fffffffLL)
+        return fail(NLSPN_EINVAL, "gconv16: problem too large");
+    NLSPN_TRY(set_lds_attr(p.fn, p.lds));
+    void *args[] = {&a};
+    return launch_kernel(p.fn, dim3((unsigned)nwg), dim3(kGcNT), args, (size_t)p.lds, as_stream(stream), "nlspn_gconv16");
 }
 
 }  // extern "C"

@@ -59,6 +59,28 @@ enum { kGcActNone = 0, kGcActRelu = 1, kGcActTanh = 2 };
     X(35, kGcS2, 1, 1, 1, 4, 10, 72, 8, kGcEpiDact)                \
     X(36, kGcS1, 2, 2, 2, 2, 8, 40, 8, kGcEpiDact)
 
+// The f16-operand family (nlspn_gconv16.h, presets NLSPN_GC16_* of include/nlspn_prop.h):
+// X(id, MODE, WM, WN, WGM, WGN, XR, XP, CCB, EPI).  XP counts 16-byte cells (eight channels of one
+// pixel) and CCB the 8-channel blocks of a chunk (4: one k-step of the 16x16x32 MFMA per tap).
+// The pixel tiling is gc_tile / gc_window's, unchanged.  Instantiated in nlspn_kern_gconv16.hip.
+#define NLSPN_GC16_CONFIGS(X)                                      \
+    X(48, kGcS2, 2, 2, 2, 2, 12, 40, 4, kGcEpiAct)                 \
+    X(49, kGcS1, 2, 2, 2, 2, 6, 40, 4, kGcEpiGru1)                 \
+    X(50, kGcS1, 2, 2, 2, 2, 6, 40, 4, kGcEpiGru2)                 \
+    X(51, kGcT2, 2, 2, 2, 2, 6, 40, 4, kGcEpiAct)                  \
+    X(52, kGcT2, 1, 2, 1, 4, 6, 80, 4, kGcEpiAct)
+
+// The LDS bytes of an f16 preset: two stages of a chunk's weights [CCB][taps][WGCO] and window
+// [CCB][XR][XP], in 16-byte cells, each region rounded up to whole LDS-DMA rounds of the
+// workgroup (one cell per lane).  Gc16Cfg (nlspn_gconv16.h) uses these very functions.
+constexpr int kGc16LdsBudget = 160 * 1024;
+NLSPN_HD constexpr int gc16_round(int v, int m) { return (v + m - 1) / m * m; }
+NLSPN_HD constexpr int gc16_wst(int mode, int wgco, int ccb) { return gc16_round(ccb * (mode == kGcT2 ? 4 : 9) * wgco, kGcNT); }
+NLSPN_HD constexpr int gc16_xst(int xr, int xp, int ccb) { return gc16_round(ccb * xr * xp, kGcNT); }
+NLSPN_HD constexpr int gc16_lds_bytes(int mode, int wgco, int xr, int xp, int ccb) {
+    return 2 * (gc16_wst(mode, wgco, ccb) + gc16_xst(xr, xp, ccb)) * 16;
+}
+
 // What a configuration's template arguments fix of the tiling: a workgroup of WGM x WGN waves,
 // each WM x WN 16x16 blocks, owns WGCO output channels x NPX pixels; its LDS input window has
 // XR rows of pitch XP words.

@@ -35,6 +35,15 @@ The forward values are those of the inference launches, bit for bit.  Under grad
 Weights are packed once per weight version into the kernels' layout and cached
 (``GruConvs.pack``), the adjoint packs beside the forward ones on the first call under
 gradients.  ``GruConvs.stats`` counts the launches per kind.
+
+Opt-in at inference (``NLSPNModel.gru_precision = "fp16"``) the same layers run on the f16
+matrix cores (``nlspn_gconv16``, ``csrc/nlspn_gconv16.h``): half operands (weights rounded once
+when packed by ``pack_conv16`` / ``pack_convt16``, activations once in the epilogue that produces
+them), f32 accumulation and epilogues, the ConvGRU state carried in f32 beside an f16 copy,
+activations between the layers in the ``c8`` layout (``to_c8`` / ``from_c8``: tests and
+boundaries only).  ``encode_dep16`` / ``encode_aff16`` / ``gru16`` / ``decode_aff16`` are the
+variants; the f16 packs live in the f32 packs' cache entry (``pack16``), ``stats["fwd16"]``
+counts their launches.  The last decoder layer stays the f32 ``nlspn_gconv_affnorm``.
 """
 from __future__ import annotations
 
@@ -45,11 +54,14 @@ import torch.nn as nn
 
 from . import _lib
 
-__all__ = ["GruConvs", "pack_adjoint", "pack_adjoint_s1", "unpack_conv", "unpack_convt", "GC_S2", "GC_S2_C16", "GC_GRU1", "GC_GRU2", "GC_T2", "GC_T2_C16", "GC_S2_SMALL"]
+__all__ = ["GruConvs", "pack_adjoint", "pack_adjoint_s1", "unpack_conv", "unpack_convt", "to_c8", "from_c8",
+           "pack_conv16", "pack_convt16", "unpack_conv16", "unpack_convt16", "GC_S2", "GC_S2_C16", "GC_GRU1", "GC_GRU2", "GC_T2", "GC_T2_C16", "GC_S2_SMALL"]
 
 GC_S2, GC_S2_C16, GC_GRU1, GC_GRU2, GC_T2, GC_T2_C16, GC_S2_SMALL = range(7)
 # the data-gradient presets (NLSPN_GC_DG_*): the adjoint kind's tiling, derivative epilogue
 GC_DG_T2, GC_DG_T2_C16, GC_DG_S2, GC_DG_S2_C16, GC_DG_S1 = range(32, 37)
+# the f16-operand presets (NLSPN_GC16_*, csrc/nlspn_gconv16.h)
+GC16_S2, GC16_GRU1, GC16_GRU2, GC16_T2, GC16_T2_C16, GC16_S2_SMALL = range(48, 54)
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 # the transposed conv's taps per output phase (py, px), in the kernel's order
 # (nlspn_gconv.h gc_tap): ky = 1 (py = 0) or 0, 2 (py = 1); likewise kx
@@ -158,6 +170,91 @@ def unpack_convt(w, cin, cout, layer):
     return out
 
 
+# ---------------------------------------------------------------------- f16 operands (nlspn_gconv16.h)
+def to_c8(x: torch.Tensor) -> torch.Tensor:
+    """(B, C, H, W) -> the kernels' c8 layout (B, ceil(C/8), H, W, 8) in half, pad channels zero;
+    one rounding to nearest-even.  For tests and boundaries, never on the hot path."""
+    B, C, H, W = x.shape
+    nb = (C + 7) // 8
+    y = torch.zeros((B, nb * 8, H, W), device=x.device, dtype=torch.float16)
+    y[:, :C] = x.to(torch.float16)
+    return y.reshape(B, nb, 8, H, W).permute(0, 1, 3, 4, 2).contiguous()
+
+
+def from_c8(y: torch.Tensor, C: int) -> torch.Tensor:
+    """Inverse of to_c8: the (B, C, H, W) half tensor of a c8 tensor."""
+    B, nb, H, W, _ = y.shape
+    return y.permute(0, 1, 4, 2, 3).reshape(B, nb * 8, H, W)[:, :C].contiguous()
+
+
+def _layout16(layer):
+    lib = _lib.get()  # a query: no device, no launch
+    co, cc, tr = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(lib.nlspn_gconv16_pack_layout(layer, ctypes.byref(co), ctypes.byref(cc), ctypes.byref(tr)))
+    return co.value, cc.value, bool(tr.value)
+
+
+def _pad_bias(bias, cout, n, device):
+    b = torch.zeros(n, device=device, dtype=torch.float32)
+    if bias is not None:
+        b[:cout] = bias.detach().float()
+    return b
+
+
+def pack_conv16(weight: torch.Tensor, bias: torch.Tensor, layer: int):
+    """(Cout, Cin, 3, 3) conv weight -> half [co_tile][cin_pad/8][9][co_tile_width][8], rounded to
+    nearest-even once; bias f32, padded."""
+    wgco, cc, tr = _layout16(layer)
+    assert not tr
+    cout, cin = weight.shape[:2]
+    ct = (cout + wgco - 1) // wgco
+    cp = (cin + cc - 1) // cc * cc
+    w = torch.zeros((ct * wgco, cp, 9), device=weight.device, dtype=torch.float16)
+    w[:cout, :cin] = weight.detach().reshape(cout, cin, 9).to(torch.float16)
+    w = w.reshape(ct, wgco, cp // 8, 8, 9).permute(0, 2, 4, 1, 3).contiguous()
+    return w.reshape(-1), _pad_bias(bias, cout, ct * wgco, weight.device)
+
+
+def pack_convt16(weight: torch.Tensor, bias: torch.Tensor, layer: int):
+    """(Cin, Cout, 3, 3) transposed-conv weight -> half, per output phase
+    [co_tile][cin_pad/8][ntap][width][8], the phases one after another; bias f32, padded."""
+    wgco, cc, tr = _layout16(layer)
+    assert tr
+    cin, cout = weight.shape[:2]
+    ct = (cout + wgco - 1) // wgco
+    cp = (cin + cc - 1) // cc * cc
+    wd = weight.detach().to(torch.float16)
+    parts = []
+    for taps in _T_TAPS:
+        w = torch.zeros((ct * wgco, cp, len(taps)), device=weight.device, dtype=torch.float16)
+        for t, (ky, kx) in enumerate(taps):
+            w[:cout, :cin, t] = wd[:, :, ky, kx].t()
+        parts.append(w.reshape(ct, wgco, cp // 8, 8, len(taps)).permute(0, 2, 4, 1, 3).contiguous().reshape(-1))
+    return torch.cat(parts), _pad_bias(bias, cout, ct * wgco, weight.device)
+
+
+def unpack_conv16(w, cout, cin, layer):
+    """Inverse of pack_conv16: the (cout, cin, 3, 3) half tensor of a packed conv weight."""
+    wgco, cc, _ = _layout16(layer)
+    ct, cp = (cout + wgco - 1) // wgco, (cin + cc - 1) // cc * cc
+    return w.reshape(ct, cp // 8, 9, wgco, 8).permute(0, 3, 1, 4, 2).reshape(ct * wgco, cp, 3, 3)[:cout, :cin]
+
+
+def unpack_convt16(w, cin, cout, layer):
+    """Inverse of pack_convt16: the (cin, cout, 3, 3) half tensor of a packed transposed-conv weight."""
+    wgco, cc, _ = _layout16(layer)
+    ct, cp = (cout + wgco - 1) // wgco, (cin + cc - 1) // cc * cc
+    out = torch.zeros((cin, cout, 3, 3), device=w.device, dtype=w.dtype)
+    o = 0
+    for taps in _T_TAPS:
+        n = ct * cp * len(taps) * wgco
+        part = w[o:o + n].reshape(ct, cp // 8, len(taps), wgco, 8).permute(0, 3, 1, 4, 2).reshape(ct * wgco, cp, len(taps))
+        for t, (ky, kx) in enumerate(taps):
+            out[:, :, ky, kx] = part[:cout, :cin, t].t()
+        o += n
+    return out
+
+
 class _ChainFn(torch.autograd.Function):
     """A chain of stride-2 convs or transposed convs (encode_dep, encode_aff, decode_aff; one
     layer: that layer) on the HIP kernels, forward and backward.  params: weight, bias per layer."""
@@ -253,8 +350,8 @@ class GruConvs:
     def reset_stats(self):
         """Launch counts per kind since the last reset: ``fwd`` (forward launches), ``dgrad``,
         ``wgrad`` (kernel launches of the weight / bias gradients) and ``gates_bwd``; ``gru_fwd``
-        counts ConvGRU cell forwards."""
-        self.stats = {"fwd": 0, "dgrad": 0, "wgrad": 0, "gates_bwd": 0, "gru_fwd": 0}
+        counts ConvGRU cell forwards; ``fwd16`` the forward launches of the f16-operand family."""
+        self.stats = {"fwd": 0, "dgrad": 0, "wgrad": 0, "gates_bwd": 0, "gru_fwd": 0, "fwd16": 0}
 
     @staticmethod
     def supported(model) -> bool:
@@ -334,6 +431,112 @@ class GruConvs:
             self._pack_adjoints(model, packed)
         self._entries[params[0].device] = (key, packed)
         return packed
+
+    def pack16(self, model):
+        """The f16 packs (pack_conv16 / pack_convt16) beside the f32 ones, in the same cache entry
+        under the same invalidation key, packed when first needed."""
+        P = self.pack(model)
+        if "f16" in P:
+            return P
+        # (the f16 chains start on the VALU kernel, which reads f32 NCHW, and end on the f32 last
+        # decoder layer: the reference's architecture; anything else has no f16 kernel)
+        first = [_conv_of(seq[0]) for seq in (model.encode_dep, model.encode_aff)]
+        if any(c.out_channels != 16 or c.in_channels > 16 for c in first) or len(model.decode_aff) < 2:
+            raise NotImplementedError("gru_precision = 'fp16' needs the reference's GRU-mode layers (1 / 9 -> 16 first "
+                                      "encoder convs, at least two decoder layers)")
+        with torch.no_grad():
+            def enc(seq, last_act):
+                out = []
+                for i, s in enumerate(seq):
+                    c = _conv_of(s)
+                    act = last_act if i == len(seq) - 1 and last_act is not None else \
+                        (ACT_RELU if _has_relu(s) else ACT_NONE)
+                    if i == 0 and c.out_channels == 16 and c.in_channels <= 16:
+                        out.append(self._raw(GC16_S2_SMALL, c, act))
+                    else:
+                        out.append(_Layer(GC16_S2, *pack_conv16(c.weight, c.bias, GC16_S2), c.in_channels,
+                                          c.out_channels, act, c))
+                return out
+            dec = []
+            for s in list(model.decode_aff)[:-1]:
+                c = _conv_of(s)
+                kind = GC16_T2_C16 if c.out_channels <= 16 else GC16_T2
+                dec.append(_Layer(kind, *pack_convt16(c.weight, c.bias, kind), c.in_channels, c.out_channels,
+                                  ACT_RELU if _has_relu(s) else ACT_NONE, c))
+            g = model.GRU
+            hc = P["hc"]
+            w1 = torch.cat([g.convz.weight, g.convr.weight, g.convq.weight], 0)
+            b1 = torch.cat([g.convz.bias, g.convr.bias, g.convq.bias], 0)
+            P["f16"] = {"dep": enc(list(model.encode_dep), None), "aff": enc(list(model.encode_aff)[:3], ACT_TANH),
+                        "dec": dec,
+                        "gru1": _Layer(GC16_GRU1, *pack_conv16(w1, b1, GC16_GRU1), 2 * hc, 3 * hc, ACT_NONE),
+                        "gru2": _Layer(GC16_GRU2, *pack_conv16(g.convq.weight[:, :hc], g.convq.bias, GC16_GRU2), hc, hc,
+                                       ACT_NONE)}
+        return P
+
+    # ------------------------------------------------------------------ f16 launches (inference)
+    def _run16(self, L, x0, c0, B, Hi, Wi, x1=None, c1=0, y16=None, y32=None, ohs=0, ows=0, in_div=1.0, h=None, zb=None,
+               rh16=None, qxb=None, hout32=None, hout16=None, hc=0):
+        _lib.call("nlspn_gconv16", x0.device, L.layer, x0, c0, x1, c1, L.w, L.b, y16, y32, h, zb, rh16, qxb, hout32,
+                  hout16, B, Hi, Wi, L.cout, ohs, ows, L.act, in_div, hc, _lib.STREAM)
+        self.stats["fwd16"] += 1
+
+    def _enc16(self, layers, x, in_div, both):
+        """A stride-2 encoder chain: f32 NCHW in, c8 between the layers and out (both: the last
+        layer also writes f32 NCHW: (y32, y16))."""
+        B, _, Hi, Wi = x.shape
+        y32 = None
+        for i, L in enumerate(layers):
+            Ho, Wo = (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1
+            y = torch.empty((B, (L.cout + 7) // 8, Ho, Wo, 8), device=x.device, dtype=torch.float16)
+            if both and i == len(layers) - 1:
+                y32 = torch.empty((B, L.cout, Ho, Wo), device=x.device, dtype=torch.float32)
+            self._run16(L, x, L.cin, B, Hi, Wi, y16=y, y32=y32, ohs=Ho, ows=Wo, in_div=in_div if i == 0 else 1.0)
+            x, Hi, Wi = y, Ho, Wo
+        return (y32, x) if both else x
+
+    def encode_dep16(self, P, new_pred, max_depth):
+        """encode_dep(new_pred / max_depth) on the f16 matrix cores: the c8 features."""
+        return self._enc16(P["f16"]["dep"], new_pred.contiguous().float(), float(max_depth), False)
+
+    def encode_aff16(self, P, aff):
+        """encode_aff on the f16 matrix cores: the initial state (h f32, its c8 copy)."""
+        return self._enc16(P["f16"]["aff"], aff.contiguous().float(), 1.0, True)
+
+    def gru16(self, P, state, x16):
+        """ConvGRU on the f16 matrix cores: state = (h f32, h c8), x16 the c8 input; the new state."""
+        self.stats["gru_fwd"] += 1
+        h, h16 = state
+        hc = P["hc"]
+        B, _, H, W = h.shape
+        z, qx, hn = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h)
+        rh16, hn16 = torch.empty_like(h16), torch.empty_like(h16)
+        F = P["f16"]
+        self._run16(F["gru1"], h16, hc, B, H, W, x1=x16, c1=hc, h=h, zb=z, rh16=rh16, qxb=qx, hc=hc)
+        self._run16(F["gru2"], rh16, hc, B, H, W, h=h, zb=z, qxb=qx, hout32=hn, hout16=hn16, hc=hc)
+        return hn, hn16
+
+    def decode_aff16(self, P, state, crop, gamma=None, kind=None):
+        """decode_aff on the f16 matrix cores up to its last layer's f32 NCHW input; the last
+        layer (16 -> K, the crop and the fused normalisation) is the f32 family's, unchanged."""
+        x = state[1]
+        B, _, Hi, Wi, _ = x.shape
+        layers = P["f16"]["dec"]
+        y32 = None
+        for i, L in enumerate(layers):
+            Ho, Wo = 2 * Hi, 2 * Wi
+            last = i == len(layers) - 1
+            if last:
+                y32 = torch.empty((B, L.cout, Ho, Wo), device=x.device, dtype=torch.float32)
+                self._run16(L, x, L.cin, B, Hi, Wi, y32=y32, ohs=Ho, ows=Wo)
+            else:
+                y = torch.empty((B, (L.cout + 7) // 8, Ho, Wo, 8), device=x.device, dtype=torch.float16)
+                self._run16(L, x, L.cin, B, Hi, Wi, y16=y, ohs=Ho, ows=Wo)
+                x = y
+            Hi, Wi = Ho, Wo
+        Pl = dict(P)
+        Pl["dec"] = P["dec"][-1:]
+        return self.decode_aff(Pl, y32, crop, gamma=gamma, kind=kind)
 
     # ------------------------------------------------------------------ launches
     @staticmethod

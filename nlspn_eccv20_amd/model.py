@@ -254,9 +254,28 @@ class NLSPNModel(nn.Module):
         # native_gru = False keeps the torch modules everywhere (A/B, tests)
         self.native_gru = True
         self.native_gru_train = False
+        # gru_precision = "fp16": at inference, where the HIP path runs, the same convolutions on
+        # the f16 matrix cores (gru.py, nlspn_gconv16.h; f32 accumulation and epilogues, f32 state).
+        # "fp32" (default) is the path above, bit for bit; ignored under gradients and with
+        # native_gru = False.  Off by default whatever the speed: the numerics differ
+        self.gru_precision = "fp32"
         self._gru_convs = GruConvs()
         params = nn.ParameterList([p for p in self.parameters() if p.requires_grad])
         self.param_groups = [{"params": params, "lr": args.lr}]
+
+    @property
+    def gru_precision(self) -> str:
+        return self._gru_precision
+
+    @gru_precision.setter
+    def gru_precision(self, value):
+        if value not in ("fp32", "fp16"):
+            raise ValueError(f"gru_precision must be 'fp32' or 'fp16', got {value!r}")
+        object.__setattr__(self, "_gru_precision", value)
+
+    def _gru_fp16(self, x) -> bool:
+        """The f16-operand convolutions run: asked for, gradients off, and the HIP path would run."""
+        return self.gru_precision == "fp16" and not torch.is_grad_enabled() and self._native_gru(x)
 
     def gru_channels_last(self):
         """Put the GRU-mode convolutions (ConvGRU, encode_aff / encode_dep, decode_aff) in
@@ -332,6 +351,13 @@ class NLSPNModel(nn.Module):
 
     def _aff_head(self, aff_feat):
         """nlspnmodel.py:228-234 (+ the _clip_as crop :237-250)."""
+        if isinstance(aff_feat, tuple):  # the fp16 path's state (h f32, h c8), _gru_update
+            gc = self._gru_convs
+            aff = gc.decode_aff16(gc.pack16(self), aff_feat, (self.args.patch_height, self.args.patch_width),
+                                  gamma=self.aff_scale_const, kind=self.args.affinity)
+            if aff.shape[1] == self.num_neighbors + 1:
+                return aff
+            return affinity_normalization(aff, self.aff_scale_const, self.args.affinity)
         if self._native_gru(aff_feat):
             gc = self._gru_convs
             # (K = 8: the last transposed conv normalises in its epilogue, nlspn_gconv_affnorm)
@@ -434,6 +460,13 @@ class NLSPNModel(nn.Module):
     def _gru_update(self, aff_feat, aff, new_pred, k):
         """nlspnmodel.py:365-371: encode the new depth, (at the first update) encode the
         affinity, one ConvGRU step."""
+        if self._gru_fp16(new_pred):
+            gc = self._gru_convs
+            P = gc.pack16(self)
+            dep16 = gc.encode_dep16(P, new_pred, self.args.max_depth)
+            if k == 2:
+                aff_feat = gc.encode_aff16(P, aff)
+            return gc.gru16(P, aff_feat, dep16)
         if self._native_gru(new_pred):
             gc = self._gru_convs
             P = gc.pack(self)
