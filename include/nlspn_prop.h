@@ -475,6 +475,14 @@ int nlspn_gconv_affnorm(const float *x0, int c0, const float *wpk, const float *
  * (nlspn_gconv_wgrad_workspace_bytes); a second launch sums them in a fixed order: no
  * atomics, bit-reproducible.
  *
+ * nlspn_gconv_wgrad_bf16x3 (opt-in; csrc/nlspn_gwgrad16.h): the same call, arguments and
+ * validation with the products on the bf16 matrix cores.  Each f32 operand a is split while
+ * staging into hi = bf16(a), lo = bf16(a - hi) (round to nearest even) and the kernel sums
+ * s_hi l_hi + s_hi l_lo + s_lo l_hi in f32: a term is off by at most 3 * 2^-18 |s l|.  Slabs,
+ * slab reduce, scale and db are the f32 entry's (db is bit-equal); its workspace query is
+ * nlspn_gconv_wgrad_bf16x3_workspace_bytes.  Nothing is clamped (an inf operand gives NaN).
+ * Shapes with both channel counts <= 16 are forwarded to nlspn_gconv_wgrad, bit for bit.
+ *
  * ConvGRU: nlspn_gconv_gru_train is the NLSPN_GC_GRU1 (stage 1: x0 = h, x1 = x, also stores r
  * into rb) / NLSPN_GC_GRU2 (stage 2: x0 = r*h, also stores q into qb) launch of nlspn_gconv,
  * bit-identical in its other outputs.  nlspn_gconv_gru_gates_backward: stage 1 du_q = dh' z
@@ -494,6 +502,10 @@ size_t nlspn_gconv_wgrad_workspace_bytes(int stride, int Cs, int Cl, int B, int 
 int nlspn_gconv_wgrad(int stride, const float *s, int Cs, const float *l0, int c0, const float *l1, int c1, float *dw,
                       float *db, int bias_from_large, float scale, void *workspace, int64_t workspace_bytes, int B,
                       int Hs, int Ws, int Hl, int Wl, void *stream);
+size_t nlspn_gconv_wgrad_bf16x3_workspace_bytes(int stride, int Cs, int Cl, int B, int Hs, int Ws, int Hl, int Wl);
+int nlspn_gconv_wgrad_bf16x3(int stride, const float *s, int Cs, const float *l0, int c0, const float *l1, int c1,
+                             float *dw, float *db, int bias_from_large, float scale, void *workspace,
+                             int64_t workspace_bytes, int B, int Hs, int Ws, int Hl, int Wl, void *stream);
 int nlspn_gconv_gru_train(int stage, const float *x0, const float *x1, int c1, const float *wpk, const float *bias,
                           const float *h, float *zb, float *rhb, float *qxb, float *hout, float *rb, float *qb, int B,
                           int H, int W, int hc, void *stream);

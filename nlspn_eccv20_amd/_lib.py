@@ -84,6 +84,9 @@ SIGNATURES = {
     "nlspn_gconv_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "nlspn_gconv_wgrad": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, ctypes.c_float, _vp, _i64, _i, _i, _i, _i,
                                _i, _vp]),
+    "nlspn_gconv_wgrad_bf16x3_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "nlspn_gconv_wgrad_bf16x3": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, ctypes.c_float, _vp, _i64, _i, _i, _i,
+                                      _i, _i, _vp]),
     "nlspn_gconv_gru_train": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
                                    _vp]),
     "nlspn_gconv_gru_gates_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -97,7 +100,8 @@ SIGNATURES = {
 AB_OPTIONAL = frozenset({"nlspn_resident_status", "nlspn_resident_config", "nlspn_gconv_pack_layout", "nlspn_gconv",
                          "nlspn_gconv_affnorm", "nlspn_gconv_dgrad", "nlspn_gconv_wgrad_workspace_bytes",
                          "nlspn_gconv_wgrad", "nlspn_gconv_gru_train", "nlspn_gconv_gru_gates_backward",
-                         "nlspn_gconv16_pack_layout", "nlspn_gconv16"})
+                         "nlspn_gconv16_pack_layout", "nlspn_gconv16",
+                         "nlspn_gconv_wgrad_bf16x3_workspace_bytes", "nlspn_gconv_wgrad_bf16x3"})
 
 _lib = None
 

@@ -5,6 +5,7 @@
 #include "nlspn_host.h"
 #include "nlspn_gconv_bwd.h"
 #include "nlspn_gconv16.h"
+#include "nlspn_gwgrad16.h"
 
 namespace nlspn {
 // defined in nlspn_kern_gconv.hip
@@ -19,6 +20,9 @@ NLSPN_GW_CONFIGS(NLSPN_GW_EXTERN)
 #define NLSPN_GC16_EXTERN(id, ...) extern template __global__ void gconv16_kernel<__VA_ARGS__>(Gconv16Args);
 NLSPN_GC16_CONFIGS(NLSPN_GC16_EXTERN)
 extern template __global__ void gsmall16_kernel<16>(Gconv16Args, const float *);
+// defined in nlspn_kern_gwgrad16.hip
+#define NLSPN_GW16_EXTERN(...) extern template __global__ void gwgrad16_kernel<__VA_ARGS__>(GwgradArgs);
+NLSPN_GW16_CONFIGS(NLSPN_GW16_EXTERN)
 }  // namespace nlspn
 
 using namespace nlspn;
@@ -286,6 +290,91 @@ int nlspn_gconv_wgrad(int stride, const float *s, int Cs, const float *l0, int c
         void *rargs[] = {&cpart, &db, &C, &one, &one, &one, &bslab, &nsb, &unit};
         NLSPN_TRY(launch_kernel(reinterpret_cast<const void *>(&gwgrad_reduce_kernel), dim3(elementwise_grid(C)), dim3(256),
                                 rargs, 0, st, "nlspn_gconv_wgrad bias reduce"));
+    }
+    return NLSPN_OK;
+}
+
+// ---- the split-bf16 weight gradient (nlspn_gwgrad16.h): the same call on the bf16 matrix cores
+}  // extern "C"
+namespace {
+template <int S, int WM, int WGM, int WGN>
+const void *gw16_fn(const Gw16Geo &g) {
+    return g.S == S && g.wm == WM && g.wgm == WGM && g.wgn == WGN
+               ? reinterpret_cast<const void *>(&gwgrad16_kernel<S, WM, WGM, WGN>) : nullptr;
+}
+const void *gw16_kernel_of(const Gw16Geo &g) {
+    const void *fn = nullptr;
+#define NLSPN_GW16_PICK(...) if (!fn) fn = gw16_fn<__VA_ARGS__>(g);
+    NLSPN_GW16_CONFIGS(NLSPN_GW16_PICK)
+    return fn;
+}
+}  // namespace
+extern "C" {
+
+size_t nlspn_gconv_wgrad_bf16x3_workspace_bytes(int stride, int Cs, int Cl, int B, int Hs, int Ws, int Hl, int Wl) {
+    GwPlan f32;
+    if (gw_plan(stride, Cs, Cl, B, Hs, Ws, Hl, Wl, f32)) return 0;  // (the shape rules are the f32 entry's)
+    if (gw16_choose(stride, Cs, Cl) == kGw16F32) return (size_t)f32.floats * sizeof(float);
+    return (size_t)gw16_plan(stride, Cs, Cl, B, Hs, Ws, Hl, Wl).floats * sizeof(float);
+}
+
+int nlspn_gconv_wgrad_bf16x3(int stride, const float *s, int Cs, const float *l0, int c0, const float *l1, int c1,
+                             float *dw, float *db, int bias_from_large, float scale, void *workspace,
+                             int64_t workspace_bytes, int B, int Hs, int Ws, int Hl, int Wl, void *stream) {
+    if (!s || !l0 || !dw || !workspace) return fail(NLSPN_EINVAL, "gconv wgrad: null tensor, gradient or workspace");
+    if (c0 < 1 || c1 < 0 || (c1 > 0 && !l1)) return fail(NLSPN_EINVAL, "gconv wgrad: bad channels c0=%d c1=%d", c0, c1);
+    if (c1 > 0 && c0 % 16 != 0)
+        return fail(NLSPN_EINVAL, "gconv wgrad: a channel block would straddle the two sources (c0 = %d, not a multiple of 16)", c0);
+    if (db && bias_from_large && c1 > 0) return fail(NLSPN_EINVAL, "gconv wgrad: the bias gradient reads one source");
+    const int Cl = c0 + c1;
+    GwPlan f32;
+    NLSPN_TRY(gw_plan(stride, Cs, Cl, B, Hs, Ws, Hl, Wl, f32));
+    // both channel counts <= 16: the one-wave f32 kernel, bit for bit (its cost is staging, not MFMA)
+    if (gw16_choose(stride, Cs, Cl) == kGw16F32)
+        return nlspn_gconv_wgrad(stride, s, Cs, l0, c0, l1, c1, dw, db, bias_from_large, scale, workspace, workspace_bytes,
+                                 B, Hs, Ws, Hl, Wl, stream);
+    const Gw16Plan pl = gw16_plan(stride, Cs, Cl, B, Hs, Ws, Hl, Wl);
+    if (workspace_bytes < pl.floats * (long long)sizeof(float))
+        return fail(NLSPN_EINVAL, "gconv wgrad: workspace too small (%lld bytes, needs %lld)", (long long)workspace_bytes,
+                    pl.floats * (long long)sizeof(float));
+    // (the kernel's per-thread staging offsets are 32 bits: a pass's 8 channel planes and one window row)
+    if ((long long)pl.mtiles * pl.ntiles * pl.nsl > 0x7fffffffLL || (long long)Hs * Ws > (1LL << 27) || (long long)Hl * Wl > (1LL << 27))
+        return fail(NLSPN_EINVAL, "gconv wgrad: problem too large");
+    const void *fn = gw16_kernel_of(pl.g);
+    if (!fn) return fail(NLSPN_EUNSUPPORTED, "gconv wgrad bf16x3: no kernel for tiling %d", pl.tiling);
+    GwgradArgs a{};
+    a.s = s; a.l0 = l0; a.l1 = l1; a.ws = static_cast<float *>(workspace);
+    a.Cs = Cs; a.c0 = c0; a.c1 = c1; a.B = B; a.Hs = Hs; a.Ws = Ws; a.Hl = Hl; a.Wl = Wl;
+    a.mtiles = pl.mtiles; a.ntiles = pl.ntiles; a.nsl = pl.nsl;
+    a.bw = pl.bw; a.nbands = pl.nbands; a.units = pl.units; a.ups = pl.ups;
+    hipStream_t st = as_stream(stream);
+    NLSPN_TRY(set_lds_attr(fn, pl.g.lds_bytes()));
+    void *args[] = {&a};
+    NLSPN_TRY(launch_kernel(fn, dim3((unsigned)(pl.mtiles * pl.ntiles * pl.nsl)), dim3(pl.g.nthr()), args,
+                            (size_t)pl.g.lds_bytes(), st, "nlspn_gconv_wgrad_bf16x3"));
+    {   // the slab reduce: the f32 entry's kernel and order
+        const float *wsp = a.ws;
+        int n0 = Cs, n1 = Cl, n1p = pl.ntiles * pl.g.nt(), T = 9, nsl = pl.nsl;
+        long long slab = pl.slab;
+        void *rargs[] = {&wsp, &dw, &n0, &n1, &n1p, &T, &slab, &nsl, &scale};
+        NLSPN_TRY(launch_kernel(reinterpret_cast<const void *>(&gwgrad_reduce_kernel),
+                                dim3(elementwise_grid((long long)Cs * Cl * 9)), dim3(256), rargs, 0, st,
+                                "nlspn_gconv_wgrad_bf16x3 reduce"));
+    }
+    if (db) {  // the bias gradient: the f32 entry's launches with its slice count (bit-equal)
+        const float *g = bias_from_large ? l0 : s;
+        int C = bias_from_large ? Cl : Cs, nsb = f32.nsb, one = 1;
+        long long HW = bias_from_large ? (long long)Hl * Wl : (long long)Hs * Ws;
+        float *part = a.ws + pl.bias_off;
+        void *pargs[] = {&g, &part, &C, &B, &HW, &nsb};
+        NLSPN_TRY(launch_kernel(reinterpret_cast<const void *>(&gbias_partial_kernel), dim3((unsigned)(C * nsb)), dim3(256),
+                                pargs, 0, st, "nlspn_gconv_wgrad_bf16x3 bias"));
+        const float *cpart = part;
+        long long bslab = C;
+        float unit = 1.f;
+        void *rargs[] = {&cpart, &db, &C, &one, &one, &one, &bslab, &nsb, &unit};
+        NLSPN_TRY(launch_kernel(reinterpret_cast<const void *>(&gwgrad_reduce_kernel), dim3(elementwise_grid(C)), dim3(256),
+                                rargs, 0, st, "nlspn_gconv_wgrad_bf16x3 bias reduce"));
     }
     return NLSPN_OK;
 }

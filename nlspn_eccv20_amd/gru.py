@@ -44,6 +44,11 @@ activations between the layers in the ``c8`` layout (``to_c8`` / ``from_c8``: te
 boundaries only).  ``encode_dep16`` / ``encode_aff16`` / ``gru16`` / ``decode_aff16`` are the
 variants; the f16 packs live in the f32 packs' cache entry (``pack16``), ``stats["fwd16"]``
 counts their launches.  The last decoder layer stays the f32 ``nlspn_gconv_affnorm``.
+
+Opt-in under gradients (``GruConvs.wgrad_precision = "bf16x3"``, set through
+``NLSPNModel.gru_wgrad_precision``) the weight gradients run on the bf16 matrix cores with each
+f32 operand split into two bf16 parts (``nlspn_gconv_wgrad_bf16x3``, ``csrc/nlspn_gwgrad16.h``);
+everything else of the backward is the same launches, and ``stats["wgrad_x3"]`` counts them.
 """
 from __future__ import annotations
 
@@ -345,13 +350,18 @@ class GruConvs:
     def __init__(self):
         self._entries = {}
         self._ws = {}  # (device, stream) -> the weight-gradient workspace
+        # "bf16x3": the weight gradients on the bf16 matrix cores with split operands
+        # (nlspn_gconv_wgrad_bf16x3, csrc/nlspn_gwgrad16.h); "fp32" (default): nlspn_gconv_wgrad
+        self.wgrad_precision = "fp32"
         self.reset_stats()
 
     def reset_stats(self):
         """Launch counts per kind since the last reset: ``fwd`` (forward launches), ``dgrad``,
         ``wgrad`` (kernel launches of the weight / bias gradients) and ``gates_bwd``; ``gru_fwd``
-        counts ConvGRU cell forwards; ``fwd16`` the forward launches of the f16-operand family."""
-        self.stats = {"fwd": 0, "dgrad": 0, "wgrad": 0, "gates_bwd": 0, "gru_fwd": 0, "fwd16": 0}
+        counts ConvGRU cell forwards; ``fwd16`` the forward launches of the f16-operand family;
+        ``wgrad_x3`` the weight / bias gradient launches of the ``"bf16x3"`` mode, counted as
+        ``wgrad`` counts the f32 entry's."""
+        self.stats = {"fwd": 0, "dgrad": 0, "wgrad": 0, "gates_bwd": 0, "gru_fwd": 0, "fwd16": 0, "wgrad_x3": 0}
 
     @staticmethod
     def supported(model) -> bool:
@@ -663,19 +673,24 @@ class GruConvs:
         return self._wgrad_raw(2, g, xin, None, False, scale)
 
     def _wgrad_raw(self, stride, s, l0, l1, bias_from_large, scale):
-        """(dW (Cs, Cl, 3, 3), db) of nlspn_gconv_wgrad: s the small tensor, l0 (+ l1) the large one."""
+        """(dW (Cs, Cl, 3, 3), db) of nlspn_gconv_wgrad (wgrad_precision = "bf16x3": of
+        nlspn_gconv_wgrad_bf16x3): s the small tensor, l0 (+ l1) the large one."""
+        if self.wgrad_precision not in ("fp32", "bf16x3"):
+            raise ValueError(f"wgrad_precision must be 'fp32' or 'bf16x3', got {self.wgrad_precision!r}")
+        x3 = self.wgrad_precision == "bf16x3"
+        name = "nlspn_gconv_wgrad_bf16x3" if x3 else "nlspn_gconv_wgrad"
         lib = _lib.get()
         B, Cs, Hs, Ws = s.shape
         c0, c1 = l0.shape[1], 0 if l1 is None else l1.shape[1]
         Hl, Wl = l0.shape[2:]
-        need = lib.nlspn_gconv_wgrad_workspace_bytes(stride, Cs, c0 + c1, B, Hs, Ws, Hl, Wl)
+        need = getattr(lib, name + "_workspace_bytes")(stride, Cs, c0 + c1, B, Hs, Ws, Hl, Wl)
         key = (s.device, torch.cuda.current_stream(s.device).cuda_stream)
         ws = self._ws.get(key)
         if ws is None or ws.numel() * 4 < need:
             ws = self._ws[key] = torch.empty((need + 3) // 4, device=s.device, dtype=torch.float32)
         dw = torch.empty((Cs, c0 + c1, 3, 3), device=s.device, dtype=torch.float32)
         db = torch.empty(c0 if bias_from_large else Cs, device=s.device, dtype=torch.float32)
-        _lib.call("nlspn_gconv_wgrad", s.device, stride, s, Cs, l0, c0, l1, c1, dw, db, int(bias_from_large), scale,
+        _lib.call(name, s.device, stride, s, Cs, l0, c0, l1, c1, dw, db, int(bias_from_large), scale,
                   ws, ws.numel() * 4, B, Hs, Ws, Hl, Wl, _lib.STREAM)
-        self.stats["wgrad"] += 4
+        self.stats["wgrad_x3" if x3 else "wgrad"] += 4
         return dw, db

@@ -260,6 +260,11 @@ class NLSPNModel(nn.Module):
         # native_gru = False.  Off by default whatever the speed: the numerics differ
         self.gru_precision = "fp32"
         self._gru_convs = GruConvs()
+        # gru_wgrad_precision = "bf16x3": where the native training path runs (native_gru_train,
+        # gradients on), the weight gradients on the bf16 matrix cores with split operands
+        # (csrc/nlspn_gwgrad16.h); forward, data gradients and gate derivatives
+        # are unchanged.  "fp32" (default) is the path above, bit for bit; ignored everywhere else
+        self.gru_wgrad_precision = "fp32"
         params = nn.ParameterList([p for p in self.parameters() if p.requires_grad])
         self.param_groups = [{"params": params, "lr": args.lr}]
 
@@ -272,6 +277,16 @@ class NLSPNModel(nn.Module):
         if value not in ("fp32", "fp16"):
             raise ValueError(f"gru_precision must be 'fp32' or 'fp16', got {value!r}")
         object.__setattr__(self, "_gru_precision", value)
+
+    @property
+    def gru_wgrad_precision(self) -> str:
+        return self._gru_convs.wgrad_precision
+
+    @gru_wgrad_precision.setter
+    def gru_wgrad_precision(self, value):
+        if value not in ("fp32", "bf16x3"):
+            raise ValueError(f"gru_wgrad_precision must be 'fp32' or 'bf16x3', got {value!r}")
+        self._gru_convs.wgrad_precision = value
 
     def _gru_fp16(self, x) -> bool:
         """The f16-operand convolutions run: asked for, gradients off, and the HIP path would run."""
