@@ -269,14 +269,54 @@ static REAL FN(orc_coord_weight)(REAL h, REAL w, int H, int W, const REAL *im, i
     return weight;
 }
 
-int FN(orc_propagate_backward)(const REAL *pred_init, const REAL *dep, const REAL *conf,
+/* Magnitude twin of orc_coord_weight: every term of the coordinate weight in absolute
+ * value, in the same order (|w_c| |f_c| summed over the corners the weight uses). */
+static REAL FN(orc_coord_weight_abs)(REAL h, REAL w, int H, int W, const REAL *im, int dir)
+{
+    if (h <= -1 || h >= H || w <= -1 || w >= W) return 0;
+    int h_low = (int)FLOOR(h), w_low = (int)FLOOR(w);
+    int h_high = h_low + 1, w_high = w_low + 1;
+    REAL weight = 0;
+    const REAL a0 = dir == 0 ? FABS(w_low + 1 - w) : FABS(h_low + 1 - h);
+    const REAL a1 = dir == 0 ? FABS(w - w_low) : FABS(h - h_low);
+    /* dir 0: corners (ll, lh, hl, hh) carry (a0, a1, a0, a1); dir 1: (a0, a0, a1, a1) */
+    const REAL c_lh = dir == 0 ? a1 : a0, c_hl = dir == 0 ? a0 : a1;
+    if (h_low >= 0 && w_low >= 0) weight += a0 * FABS(im[(long long)h_low * W + w_low]);
+    if (h_low >= 0 && w_high <= W - 1) weight += c_lh * FABS(im[(long long)h_low * W + w_high]);
+    if (h_high <= H - 1 && w_low >= 0) weight += c_hl * FABS(im[(long long)h_high * W + w_low]);
+    if (h_high <= H - 1 && w_high <= W - 1) weight += a1 * FABS(im[(long long)h_high * W + w_high]);
+    return weight;
+}
+
+/* orc_propagate_backward with an optional magnitude pass (b_pred_init != NULL selects it).
+ * Beside every gradient the pass carries the sum of the absolute values of the terms
+ * added into it through the same linear recurrence, with the same gates:
+ *   b_go = |1-m| b_gp;  b_gaff[tap] += b_go bilinear(|f|);
+ *   b_goff += b_go |a| sum_corners |w_c| |f_c|;  scatter b_go |a| w;
+ *   b_gcf += b_gf |p|;  b_gp = b_gf |cf| + |grad_inter|;
+ * and through the normalisation backward G_k = b_gaff[tap] + b_gaff[ref],
+ * dot = sum G_k |u_k|, b_gu = G/se + dot/se^2 (the dot term only where the real pass has
+ * it), b_ga = b_gu (1-th^2)/d, b_gamma = sum b_gu |th| / d^2.
+ * Outputs of the pass: b_* of the gradients' shapes; g_aff_norm / b_aff_norm (optional,
+ * B x (K+1) planes): the gradient of the normalised affinities before the normalisation
+ * backward and its bound; c_aff_raw (optional, shape of grad_aff_raw) = b_gu th^2 / d for the
+ * tanh kinds, else 0: the weight of the subtraction 1 - th^2, which the magnitude pass carries
+ * as one factor (a rounding of th or th^2 moves the gradient by that many times its relative
+ * size); mass (T x B, row t-1 for iteration t) = sum_pixels |go_t|
+ * (sum over the K+1 taps of |a|); info[0] = max_pixel sum |a|, info[1] = smallest non-zero
+ * |pre_t| over the clamped values (every t under always_clip, else t = T only), info[2] =
+ * smallest |s - 1| (ASS/TGASS, else +inf), info[3] = smallest non-zero |u_k|. */
+int FN(orc_propagate_backward_ex)(const REAL *pred_init, const REAL *dep, const REAL *conf,
                                const REAL *aff_raw, long long aff_bstride,
                                const REAL *off_raw, long long off_bstride,
                                REAL gamma, int kind, int kh, int kw, int T, unsigned flags,
                                int B, int H, int W,
                                const REAL *grad_pred, const REAL *grad_inter,
                                REAL *grad_pred_init, REAL *grad_conf, REAL *grad_aff_raw,
-                               REAL *grad_off_raw, REAL *grad_gamma)
+                               REAL *grad_off_raw, REAL *grad_gamma,
+                               REAL *b_pred_init, REAL *b_conf, REAL *b_aff_raw, REAL *b_off_raw,
+                               REAL *b_gamma, REAL *g_aff_norm, REAL *b_aff_norm, REAL *c_aff_raw,
+                               double *mass, double *info)
 {
     const long long HW = (long long)H * W, N = (long long)B * HW;
     const int K = kh * kw - 1, KK = K + 1, REF = K / 2;
@@ -326,16 +366,37 @@ int FN(orc_propagate_backward)(const REAL *pred_init, const REAL *dep, const REA
     REAL *gcf = (REAL *)calloc((size_t)N, sizeof(REAL));
     REAL *gp = (REAL *)calloc((size_t)N, sizeof(REAL)); /* dL/dp_t */
     REAL *gf = (REAL *)calloc((size_t)N, sizeof(REAL)); /* dL/df_{t-1} */
+    const int bnd = b_pred_init != NULL;
+    REAL *xaff = bnd ? (REAL *)calloc((size_t)KK * N, sizeof(REAL)) : NULL;
+    REAL *xoff = bnd ? (REAL *)calloc((size_t)2 * KK * N, sizeof(REAL)) : NULL;
+    REAL *xcf = bnd ? (REAL *)calloc((size_t)N, sizeof(REAL)) : NULL;
+    REAL *xp = bnd ? (REAL *)calloc((size_t)N, sizeof(REAL)) : NULL;
+    REAL *xf = bnd ? (REAL *)calloc((size_t)N, sizeof(REAL)) : NULL;
+    REAL *fa = bnd ? (REAL *)calloc((size_t)N, sizeof(REAL)) : NULL; /* |f_{t-1}| */
+    double amax = 0, min_pre = INFINITY, min_s1 = INFINITY, min_u = INFINITY;
+    if (bnd)
+        for (int t = clip ? 0 : T; t <= T; ++t)
+            for (long long i = 0; i < N; ++i) {
+                const double v = fabs((double)pre[(long long)t * N + i]);
+                if (v != 0 && v < min_pre) min_pre = v;
+            }
     for (long long i = 0; i < N; ++i) {
         REAL g = grad_inter ? grad_inter[(long long)(T - 1) * N + i] : 0;
         if (grad_pred) g += clip ? grad_pred[i] : (p[(long long)T * N + i] >= 0 ? grad_pred[i] : 0);
         gp[i] = g;
+        if (bnd) {
+            REAL x = grad_inter ? FABS(grad_inter[(long long)(T - 1) * N + i]) : 0;
+            if (grad_pred) x += clip ? FABS(grad_pred[i]) : (p[(long long)T * N + i] >= 0 ? FABS(grad_pred[i]) : 0);
+            xp[i] = x;
+        }
     }
     for (int t = T; t >= 1; --t) {
         const REAL *pp = p + (long long)(t - 1) * N, *pr = pre + (long long)t * N;
         for (long long i = 0; i < N; ++i) f[i] = conf ? pp[i] * cf[i] : pp[i];
         for (long long i = 0; i < N; ++i) gf[i] = 0;
-        for (int b = 0; b < B; ++b)
+        if (bnd) for (long long i = 0; i < N; ++i) { xf[i] = 0; fa[i] = FABS(f[i]); }
+        for (int b = 0; b < B; ++b) {
+            double msum = 0;
             for (int y = 0; y < H; ++y)
                 for (int x = 0; x < W; ++x) {
                     const long long q = (long long)y * W + x, i = b * HW + q;
@@ -344,6 +405,17 @@ int FN(orc_propagate_backward)(const REAL *pred_init, const REAL *dep, const REA
                     const REAL go = preserve ? ((REAL)1.0 - m[i]) * g : g;
                     const REAL *fb = f + b * HW;
                     REAL *gfb = gf + b * HW;
+                    REAL xo = 0, *xfb = NULL;
+                    if (bnd) {
+                        REAL x = xp[i];
+                        if (clip && !(pr[i] >= 0)) x = 0;
+                        xo = preserve ? FABS((REAL)1.0 - m[i]) * x : x;
+                        xfb = xf + b * HW;
+                        double sa = 0;
+                        for (int tap = 0; tap < KK; ++tap) sa += fabs((double)aff[((long long)b * KK + tap) * HW + q]);
+                        if (sa > amax) amax = sa;
+                        msum += fabs((double)go) * sa;
+                    }
                     for (int tap = 0; tap < KK; ++tap) {
                         const int ii = tap / kw, jj = tap % kw;
                         const REAL a = aff[((long long)b * KK + tap) * HW + q];
@@ -373,14 +445,36 @@ int FN(orc_propagate_backward)(const REAL *pred_init, const REAL *dep, const REA
                         if (hl >= 0 && wl + 1 <= W - 1) gfb[(long long)hl * W + wl + 1] += hh * lw * top;
                         if (hl + 1 <= H - 1 && wl >= 0) gfb[(long long)(hl + 1) * W + wl] += lh * hw * top;
                         if (hl + 1 <= H - 1 && wl + 1 <= W - 1) gfb[(long long)(hl + 1) * W + wl + 1] += lh * lw * top;
+                        if (bnd) {
+                            const REAL aa = FABS(a), xtop = xo * aa;
+                            xaff[((long long)b * KK + tap) * HW + q] += xo * FN(orc_bilinear)(fa + b * HW, H, W, hs, ws);
+                            if (offi) {
+                                xoff[((long long)b * 2 * KK + 2 * tap) * HW + q] +=
+                                    FN(orc_coord_weight_abs)(hs, ws, H, W, fb, 0) * xo * aa;
+                                xoff[((long long)b * 2 * KK + 2 * tap + 1) * HW + q] +=
+                                    FN(orc_coord_weight_abs)(hs, ws, H, W, fb, 1) * xo * aa;
+                            }
+                            if (hl >= 0 && wl >= 0) xfb[(long long)hl * W + wl] += hh * hw * xtop;
+                            if (hl >= 0 && wl + 1 <= W - 1) xfb[(long long)hl * W + wl + 1] += hh * lw * xtop;
+                            if (hl + 1 <= H - 1 && wl >= 0) xfb[(long long)(hl + 1) * W + wl] += lh * hw * xtop;
+                            if (hl + 1 <= H - 1 && wl + 1 <= W - 1) xfb[(long long)(hl + 1) * W + wl + 1] += lh * lw * xtop;
+                        }
                     }
                 }
+            if (bnd && mass) mass[(long long)(t - 1) * B + b] = msum;
+        }
         /* f_{t-1} = p_{t-1} * conf' ; p_{t-1} = clamp(blend(...)) */
         for (long long i = 0; i < N; ++i) {
             if (conf) gcf[i] += gf[i] * pp[i];
             REAL g = conf ? gf[i] * cf[i] : gf[i];
             if (t - 1 >= 1 && grad_inter) g += grad_inter[(long long)(t - 2) * N + i];
             gp[i] = g;
+            if (bnd) {
+                if (conf) xcf[i] += xf[i] * FABS(pp[i]);
+                REAL x = conf ? xf[i] * FABS(cf[i]) : xf[i];
+                if (t - 1 >= 1 && grad_inter) x += FABS(grad_inter[(long long)(t - 2) * N + i]);
+                xp[i] = x;
+            }
         }
     }
     /* p_0 = clamp(blend(pred_init)) */
@@ -389,7 +483,23 @@ int FN(orc_propagate_backward)(const REAL *pred_init, const REAL *dep, const REA
         if (clip && !(pre[i] >= 0)) g = 0;
         grad_pred_init[i] = preserve ? ((REAL)1.0 - m[i]) * g : g;
         if (grad_conf) grad_conf[i] = conf ? (preserve ? ((REAL)1.0 - m[i]) * gcf[i] : gcf[i]) : 0;
+        if (bnd) {
+            REAL x = xp[i];
+            if (clip && !(pre[i] >= 0)) x = 0;
+            const REAL am = FABS((REAL)1.0 - m[i]);
+            b_pred_init[i] = preserve ? am * x : x;
+            if (b_conf) b_conf[i] = conf ? (preserve ? am * xcf[i] : xcf[i]) : 0;
+        }
     }
+    if (bnd && g_aff_norm) memcpy(g_aff_norm, gaff, sizeof(REAL) * (size_t)KK * N);
+    if (bnd && b_aff_norm) memcpy(b_aff_norm, xaff, sizeof(REAL) * (size_t)KK * N);
+    if (bnd && b_off_raw && offi)
+        for (int b = 0; b < B; ++b)
+            for (int k = 0; k < K; ++k) {
+                const int tap = k < REF ? k : k + 1;
+                for (long long q = 0; q < 2 * HW; ++q)
+                    b_off_raw[((long long)b * 2 * K + 2 * k) * HW + q] = xoff[((long long)b * 2 * KK + 2 * tap) * HW + q];
+            }
     /* _off_insert backward: drop the reference pair */
     if (grad_off_raw && offi)
         for (int b = 0; b < B; ++b)
@@ -399,7 +509,7 @@ int FN(orc_propagate_backward)(const REAL *pred_init, const REAL *dep, const REA
                     grad_off_raw[((long long)b * 2 * K + 2 * k) * HW + q] = goff[((long long)b * 2 * KK + 2 * tap) * HW + q];
             }
     /* _aff_insert + _affinity_normalization backward */
-    REAL gg = 0;
+    REAL gg = 0, xg = 0;
     for (int b = 0; b < B; ++b)
         for (long long q = 0; q < HW; ++q) {
             REAL u[64], G[64], th[64];
@@ -437,12 +547,65 @@ int FN(orc_propagate_backward)(const REAL *pred_init, const REAL *dep, const REA
                 }
                 grad_aff_raw[((long long)b * K + k) * HW + q] = ga;
             }
+            if (bnd) {
+                REAL X[64], xdot = 0;
+                const REAL xref = xaff[((long long)b * KK + REF) * HW + q];
+                for (int k = 0; k < K; ++k) {
+                    const int tap = k < REF ? k : k + 1;
+                    X[k] = xaff[((long long)b * KK + tap) * HW + q] + xref;
+                    xdot += X[k] * FABS(u[k]);
+                    const double au = fabs((double)u[k]);
+                    if (au != 0 && au < min_u) min_u = au;
+                }
+                if (kind == ORC_ASS || kind == ORC_TGASS) {
+                    const double d1 = fabs((double)s - 1.0);
+                    if (d1 < min_s1) min_s1 = d1;
+                }
+                for (int k = 0; k < K; ++k) {
+                    REAL xu;
+                    if (kind == ORC_TC) xu = X[k];
+                    else {
+                        xu = X[k] / se;
+                        if (!clamped && u[k] != 0) xu += xdot / (se * se);
+                    }
+                    REAL xa = xu;
+                    if (kind == ORC_TC) xa = xu * FABS(1 - th[k] * th[k]) / FABS(gamma);
+                    else if (kind == ORC_TGASS) {
+                        const REAL d = gamma + (REAL)1e-8;
+                        xa = xu * FABS(1 - th[k] * th[k]) / FABS(d);
+                        xg += xu * FABS(th[k]) / (d * d);
+                    }
+                    b_aff_raw[((long long)b * K + k) * HW + q] = xa;
+                    if (c_aff_raw)
+                        c_aff_raw[((long long)b * K + k) * HW + q] =
+                            kind == ORC_TC ? xu * (th[k] * th[k]) / FABS(gamma)
+                            : kind == ORC_TGASS ? xu * (th[k] * th[k]) / FABS(gamma + (REAL)1e-8) : 0;
+                }
+            }
         }
     if (grad_gamma) *grad_gamma = kind == ORC_TGASS ? gg : 0;
+    if (bnd && b_gamma) *b_gamma = kind == ORC_TGASS ? xg : 0;
+    if (bnd && info) { info[0] = amax; info[1] = min_pre; info[2] = min_s1; info[3] = min_u; }
 
     free(aff); free(offi); free(cf); free(m); free(p); free(pre); free(f);
     free(gaff); free(goff); free(gcf); free(gp); free(gf);
+    free(xaff); free(xoff); free(xcf); free(xp); free(xf); free(fa);
     return 0;
+}
+
+int FN(orc_propagate_backward)(const REAL *pred_init, const REAL *dep, const REAL *conf,
+                               const REAL *aff_raw, long long aff_bstride,
+                               const REAL *off_raw, long long off_bstride,
+                               REAL gamma, int kind, int kh, int kw, int T, unsigned flags,
+                               int B, int H, int W,
+                               const REAL *grad_pred, const REAL *grad_inter,
+                               REAL *grad_pred_init, REAL *grad_conf, REAL *grad_aff_raw,
+                               REAL *grad_off_raw, REAL *grad_gamma)
+{
+    return FN(orc_propagate_backward_ex)(pred_init, dep, conf, aff_raw, aff_bstride, off_raw, off_bstride, gamma,
+                                         kind, kh, kw, T, flags, B, H, W, grad_pred, grad_inter, grad_pred_init,
+                                         grad_conf, grad_aff_raw, grad_off_raw, grad_gamma, NULL, NULL, NULL, NULL,
+                                         NULL, NULL, NULL, NULL, NULL, NULL);
 }
 
 /* ---------------------------------------------------------------------------
@@ -524,28 +687,42 @@ static REAL FN(orc_grad_weight)(REAL ah, REAL aw, int h, int w, int H, int W)
  * im2col again -> grad_weight += grad_output_g . columns_g^T; grad_bias +=
  * grad_output_g . ones.  grad_bias may be NULL.  Returns 0, or -1 on allocation
  * failure. */
-int FN(orc_mdcn_bwd)(const REAL *in, const REAL *wt, const REAL *off, const REAL *mask, const REAL *go,
+int FN(orc_mdcn_bwd_ex)(const REAL *in, const REAL *wt, const REAL *off, const REAL *mask, const REAL *go,
                      int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                      int dh, int dw, int group, int dg, REAL *g_in, REAL *g_off, REAL *g_mask, REAL *g_wt,
-                     REAL *g_bias)
+                     REAL *g_bias, REAL *b_in, REAL *b_off, REAL *b_mask, REAL *b_wt, REAL *b_bias)
 {
     const int Ho = (H + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1, Wo = (W + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
     const int KK = kh * kw, cpg = C / group, opg = Cout / group, cpdg = C / dg;
     const long long P = (long long)Ho * Wo, BP = (long long)B * P, HW = (long long)H * W;
     REAL *col = (REAL *)malloc(sizeof(REAL) * (size_t)C * KK * (size_t)BP);
     if (!col) return -1;
+    /* magnitude pass (b_in != NULL): the same sums with every term in absolute value */
+    const int bnd = b_in != NULL;
+    REAL *xcol = NULL, *ina = NULL, *mka = NULL;
+    if (bnd) {
+        const size_t n_in = (size_t)B * C * HW, n_mk = (size_t)B * dg * KK * (size_t)P;
+        xcol = (REAL *)malloc(sizeof(REAL) * (size_t)C * KK * (size_t)BP);
+        ina = (REAL *)malloc(sizeof(REAL) * n_in);
+        mka = (REAL *)malloc(sizeof(REAL) * n_mk);
+        if (!xcol || !ina || !mka) { free(col); free(xcol); free(ina); free(mka); return -1; }
+        for (size_t k = 0; k < n_in; ++k) ina[k] = FABS(in[k]);
+        for (size_t k = 0; k < n_mk; ++k) mka[k] = FABS(mask[k]);
+    }
     /* columns (.cu:213-220) */
     for (int c = 0; c < C; ++c) {
         const int g = c / cpg, cl = c % cpg;
         for (int t = 0; t < KK; ++t)
             for (int b = 0; b < B; ++b)
                 for (long long p = 0; p < P; ++p) {
-                    REAL s = 0;
+                    REAL s = 0, xs = 0;
                     for (int ol = 0; ol < opg; ++ol) {
                         const int co = g * opg + ol;
                         s += wt[((long long)co * cpg + cl) * KK + t] * go[((long long)b * Cout + co) * P + p];
+                        xs += FABS(wt[((long long)co * cpg + cl) * KK + t]) * FABS(go[((long long)b * Cout + co) * P + p]);
                     }
                     col[((long long)c * KK + t) * BP + (long long)b * P + p] = s;
+                    if (bnd) xcol[((long long)c * KK + t) * BP + (long long)b * P + p] = xs;
                 }
     }
     /* col2im_coord (.cuh:256-328) */
@@ -554,7 +731,7 @@ int FN(orc_mdcn_bwd)(const REAL *in, const REAL *wt, const REAL *off, const REAL
             for (int oc = 0; oc < 2 * KK; ++oc)
                 for (long long p = 0; p < P; ++p) {
                     const int t = oc / 2, dir = oc % 2, ho = (int)(p / Wo), wo = (int)(p % Wo);
-                    REAL val = 0, mval = 0;
+                    REAL val = 0, mval = 0, xval = 0, xmval = 0;
                     for (int cnt = 0; cnt < cpdg; ++cnt) {
                         const int c = dgi * cpdg + cnt;
                         const REAL cv = col[((long long)c * KK + t) * BP + (long long)b * P + p];
@@ -566,15 +743,26 @@ int FN(orc_mdcn_bwd)(const REAL *in, const REAL *wt, const REAL *off, const REAL
                             ih = iw = -2;
                         } else {
                             mval += cv * FN(orc_bilinear)(im, H, W, ih, iw);
+                            if (bnd)
+                                xmval += xcol[((long long)c * KK + t) * BP + (long long)b * P + p] *
+                                         FN(orc_bilinear)(ina + ((long long)b * C + c) * HW, H, W, ih, iw);
                         }
                         const REAL weight = FN(orc_coord_weight)(ih, iw, H, W, im, dir);
                         val += weight * cv * m;
+                        if (bnd)
+                            xval += FN(orc_coord_weight_abs)(ih, iw, H, W, im, dir) *
+                                    xcol[((long long)c * KK + t) * BP + (long long)b * P + p] * FABS(m);
+                    }
+                    if (bnd) {
+                        b_off[((long long)(b * dg + dgi) * 2 * KK + oc) * P + p] = xval;
+                        if (dir == 0) b_mask[((long long)(b * dg + dgi) * KK + t) * P + p] = xmval;
                     }
                     g_off[((long long)(b * dg + dgi) * 2 * KK + oc) * P + p] = val;
                     if (dir == 0) g_mask[((long long)(b * dg + dgi) * KK + t) * P + p] = mval;
                 }
     /* col2im (.cuh:196-254), pad_w := pad_h as the reference's call passes it */
     memset(g_in, 0, sizeof(REAL) * (size_t)B * C * HW);
+    if (bnd) memset(b_in, 0, sizeof(REAL) * (size_t)B * C * HW);
     for (int c = 0; c < C; ++c)
         for (int t = 0; t < KK; ++t)
             for (int b = 0; b < B; ++b)
@@ -591,6 +779,9 @@ int FN(orc_mdcn_bwd)(const REAL *in, const REAL *wt, const REAL *off, const REAL
                             if (y >= 0 && y < H && x >= 0 && x < W && FABS(ih - y) < 1 && FABS(iw - x) < 1) {
                                 const REAL weight = FN(orc_grad_weight)(ih, iw, y, x, H, W);
                                 g_in[((long long)b * C + c) * HW + (long long)y * W + x] += weight * top;
+                                if (bnd)
+                                    b_in[((long long)b * C + c) * HW + (long long)y * W + x] +=
+                                        FABS(weight) * (xcol[((long long)c * KK + t) * BP + (long long)b * P + p] * FABS(m));
                             }
                         }
                 }
@@ -599,21 +790,40 @@ int FN(orc_mdcn_bwd)(const REAL *in, const REAL *wt, const REAL *off, const REAL
         const int g = co / opg;
         for (int cl = 0; cl < cpg; ++cl)
             for (int t = 0; t < KK; ++t) {
-                REAL s = 0;
+                REAL s = 0, xs = 0;
                 for (int b = 0; b < B; ++b)
-                    for (long long p = 0; p < P; ++p)
+                    for (long long p = 0; p < P; ++p) {
                         s += go[((long long)b * Cout + co) * P + p] *
                              FN(orc_im2col_val)(in, off, mask, b, g * cpg + cl, t, (int)(p / Wo), (int)(p % Wo), C, H,
                                                 W, Ho, Wo, kw, KK, sh, sw, ph, pw, dh, dw, dg, cpdg, 0, 0, 0);
+                        if (bnd)
+                            xs += FABS(go[((long long)b * Cout + co) * P + p]) *
+                                  FN(orc_im2col_val)(ina, off, mka, b, g * cpg + cl, t, (int)(p / Wo), (int)(p % Wo), C,
+                                                     H, W, Ho, Wo, kw, KK, sh, sw, ph, pw, dh, dw, dg, cpdg, 0, 0, 0);
+                    }
                 g_wt[((long long)co * cpg + cl) * KK + t] = s;
+                if (bnd) b_wt[((long long)co * cpg + cl) * KK + t] = xs;
             }
         if (g_bias) {
-            REAL s = 0;
+            REAL s = 0, xs = 0;
             for (int b = 0; b < B; ++b)
-                for (long long p = 0; p < P; ++p) s += go[((long long)b * Cout + co) * P + p];
+                for (long long p = 0; p < P; ++p) {
+                    s += go[((long long)b * Cout + co) * P + p];
+                    xs += FABS(go[((long long)b * Cout + co) * P + p]);
+                }
             g_bias[co] = s;
+            if (bnd && b_bias) b_bias[co] = xs;
         }
     }
-    free(col);
+    free(col); free(xcol); free(ina); free(mka);
     return 0;
+}
+
+int FN(orc_mdcn_bwd)(const REAL *in, const REAL *wt, const REAL *off, const REAL *mask, const REAL *go,
+                     int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                     int dh, int dw, int group, int dg, REAL *g_in, REAL *g_off, REAL *g_mask, REAL *g_wt,
+                     REAL *g_bias)
+{
+    return FN(orc_mdcn_bwd_ex)(in, wt, off, mask, go, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, group, dg,
+                               g_in, g_off, g_mask, g_wt, g_bias, NULL, NULL, NULL, NULL, NULL);
 }

@@ -176,6 +176,53 @@ def propagate_backward(pred_init, dep, conf, aff_raw, off_raw, gamma, grad_pred,
             "offset": g_off, "gamma": float(g_gamma[0])}
 
 
+def propagate_backward_bound(pred_init, dep, conf, aff_raw, off_raw, gamma, grad_pred, grad_inter=None, *,
+                             kind="TGASS", kh=3, kw=3, prop_time=18, preserve_input=True, always_clip=False):
+    """propagate_backward() with the magnitude pass (orc_propagate_backward_ex): beside every
+    gradient, the sum of the absolute values of the terms added into it, carried through the
+    same recurrence.  Returns (grads, bounds, info): grads and bounds are dicts of the same
+    keys and shapes (pred_init, confidence, aff, offset, gamma); info holds
+    mass (T,B) [row t-1 = iteration t] = sum_pixels |go_t| sum_taps |a|, amax = max_pixel
+    sum_taps |a|, the kink margins min_pre / min_s1 / min_u (inf where none applies), and
+    aff_norm = (gradient, bound) of the normalised (B,K+1,H,W) affinities, and aff_cond (B,K,H,W)
+    = b_gu th^2 / d, the weight of the subtraction 1 - th^2 in the raw-affinity gradient of the
+    tanh kinds (0 for AS/ASS)."""
+    dtype = pred_init.dtype
+    sfx, cr = _sfx(dtype)
+    pred_init, dep, conf, aff_raw, off_raw, grad_pred, grad_inter = (
+        _c(x, dtype) for x in (pred_init, dep, conf, aff_raw, off_raw, grad_pred, grad_inter))
+    B, _, H, W = pred_init.shape
+    K = kh * kw - 1
+    flags = (PRESERVE if preserve_input else 0) | (ALWAYS_CLIP if always_clip else 0)
+
+    def outs():
+        return (np.zeros((B, 1, H, W), dtype=dtype), np.zeros((B, 1, H, W), dtype=dtype),
+                np.zeros((B, K, H, W), dtype=dtype),
+                None if off_raw is None else np.zeros((B, 2 * K, H, W), dtype=dtype), np.zeros(1, dtype=dtype))
+
+    g, x = outs(), outs()
+    gn, xn = (np.zeros((B, K + 1, H, W), dtype=dtype) for _ in range(2))
+    cond = np.zeros((B, K, H, W), dtype=dtype)
+    mass = np.zeros((prop_time, B), dtype=np.float64)
+    info = np.zeros(4, dtype=np.float64)
+    fn = getattr(lib(), f"orc_propagate_backward_ex_{sfx}")
+    fn.restype = ctypes.c_int
+    rc = fn(_p(pred_init), _p(dep), _p(conf), _p(aff_raw), ctypes.c_longlong(K * H * W),
+            _p(off_raw), ctypes.c_longlong(2 * K * H * W), cr(gamma), AFFINITY_KINDS[kind], kh, kw, prop_time,
+            flags, B, H, W, _p(grad_pred), _p(grad_inter), *(_p(a) for a in g), *(_p(a) for a in x),
+            _p(gn), _p(xn), _p(cond), _p(mass), _p(info))
+    if rc != 0:
+        raise ValueError(f"oracle backward rejected its arguments (code {rc})")
+
+    def pack(t):
+        return {"pred_init": t[0], "confidence": t[1] if conf is not None else None, "aff": t[2], "offset": t[3],
+                "gamma": float(t[4][0])}
+
+    return pack(g), pack(x), {"mass": mass, "amax": float(info[0]), "min_pre": float(info[1]),
+                              "min_s1": float(info[2]), "min_u": float(info[3]), "aff_norm": (gn, xn),
+                              "aff_cond": cond}
+
+
 def _mdcn_shape(H, W, kh, kw, sh, sw, ph, pw, dh, dw):
     return (H + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1, (W + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
 
@@ -214,6 +261,30 @@ def mdcn_backward(inp, weight, offset, mask, grad_output, stride=(1, 1), padding
     if rc != 0:
         raise MemoryError("oracle mdcn backward: allocation failed")
     return gi, goff, gm, gw, gb
+
+
+def mdcn_backward_bound(inp, weight, offset, mask, grad_output, stride=(1, 1), padding=(1, 1), dilation=(1, 1),
+                        group=1, deformable_group=1):
+    """mdcn_backward() with the magnitude pass: returns (grads, bounds), each a tuple
+    (input, offset, mask, weight, bias); a bound is the same sum as its gradient with every
+    term in absolute value."""
+    dtype = inp.dtype
+    sfx, _ = _sfx(dtype)
+    inp, weight, offset, mask, grad_output = (_c(x, dtype) for x in (inp, weight, offset, mask, grad_output))
+    B, C, H, W = inp.shape
+    Cout, _, kh, kw = weight.shape
+
+    def outs():
+        return tuple(np.zeros_like(x) for x in (inp, offset, mask, weight)) + (np.zeros((Cout,), dtype=dtype),)
+
+    g, x = outs(), outs()
+    fn = getattr(lib(), f"orc_mdcn_bwd_ex_{sfx}")
+    fn.restype = ctypes.c_int
+    rc = fn(_p(inp), _p(weight), _p(offset), _p(mask), _p(grad_output), B, C, H, W, Cout, kh, kw, *stride, *padding,
+            *dilation, group, deformable_group, *(_p(a) for a in g), *(_p(a) for a in x))
+    if rc != 0:
+        raise MemoryError("oracle mdcn backward: allocation failed")
+    return g, x
 
 
 def s2d_front(dep, w1, b1, w2, b2):

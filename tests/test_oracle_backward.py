@@ -7,6 +7,7 @@ affinity normalisation, blends and clamps."""
 import numpy as np
 import pytest
 
+import _bwd_cases as bc
 from nlspn_eccv20_amd.synthetic import synth
 
 EPS = 1e-6
@@ -72,3 +73,110 @@ def test_backward_matches_finite_differences(oracle, kw):
     if kw.get("kind", "TGASS") == "TGASS":
         names.append("gamma")
     _fd_check(oracle, s, kw, 3, names)
+
+
+# ------------------------------------------------------------------ magnitude pass
+# oracle.propagate_backward_bound / mdcn_backward_bound and the cases of tests/_bwd_cases.py
+# that tests/test_gpu_backward_elem.py and tests/test_gpu_dcn_elem.py check per element.
+_RUNS = {}
+
+
+def _run(oracle, name):
+    """One float64 run with the magnitude pass and one float32 run per case, shared."""
+    if name not in _RUNS:
+        oracle.set_threads(16)
+        s = bc.grid_inputs(name)
+        g64, x, info = bc.oracle_bound(oracle, name, s)
+        g32 = bc.oracle_bound(oracle, name, s, np.float32)[0]
+        _RUNS[name] = (s["aff"], g64, x, info, g32, s["cls"])
+    return _RUNS[name]
+
+
+@pytest.mark.parametrize("name", list(bc.CASES))
+def test_case_guard(oracle, name):
+    """A condition on the inputs, not a tolerance: on the float64 forward no clamped value, no
+    normaliser and no |u_k| of any case lies within GUARD of its kink, so float32 and float64
+    take the same branch everywhere and no element needs to be excluded."""
+    info, cls = _run(oracle, name)[3], _run(oracle, name)[5]
+    assert info["min_pre"] >= bc.GUARD and info["min_s1"] >= bc.GUARD and info["min_u"] >= bc.GUARD, info
+    if cls is not None:  # and the stated share of every tap class is there
+        for k in range(1, len(bc.CLASSES) + 1):
+            assert 0.5 * bc.SHARE < np.mean(cls == k) < 1.5 * bc.SHARE, (bc.CLASSES[k - 1], np.mean(cls == k))
+    aff = _run(oracle, name)[0]
+    assert np.any(aff < 0) == bc.CASES[name]["signed"]  # sign(u_k) = -1 is there where the case says so
+    if bc.CASES[name]["special"] == "nonexact":
+        # the marked pixel alone scatters more than the kernels' exact-path limit (tot < 3.0e38f),
+        # with a margin no float rounding of sum |a| closes: its window takes the float-atomic branch
+        c = bc.CASES[name]
+        assert info["mass"][c["T"] - 1, 0] >= 3.15e38 and info["mass"][c["T"] - 1, 1] < 1e30
+
+
+@pytest.mark.parametrize("name", list(bc.CASES))
+def test_bounds_dominate_gradients(oracle, name):
+    _, g64, x, info, _, _ = _run(oracle, name)
+    for t in bc.tensors_of(name):
+        assert np.all(np.asarray(x[t]) >= np.abs(np.asarray(g64[t]))), t
+    assert np.all(info["aff_norm"][1] >= np.abs(info["aff_norm"][0]))
+    assert np.all(info["mass"] > 0) and info["amax"] >= 1.0 - 1e-6
+
+
+def test_bound_pass_leaves_gradients_unchanged(oracle):
+    name = "res_tiny_parts"
+    s = bc.grid_inputs(name)
+    g64 = _run(oracle, name)[1]
+    f64 = lambda a: a.astype(np.float64)  # noqa: E731
+    ref = oracle.propagate_backward(f64(s["pred_init"]), f64(s["dep"]), f64(s["conf"]), f64(s["aff"]), f64(s["off"]),
+                                    bc.gamma_of(name), f64(s["grad_pred"]), f64(s["grad_inter"]),
+                                    **bc.oracle_kwargs(name))
+    for t in bc.TENSORS:
+        assert np.array_equal(np.asarray(ref[t]), np.asarray(g64[t])), t
+
+
+def test_bound_equals_gradient_when_every_term_is_nonnegative(oracle):
+    """Non-negative f, affinities (kind AS: a_k = |a|/s, a_ref = 1 - sum > 0) and upstream
+    gradients: no term of the recurrence is negative, so the magnitude pass repeats the
+    gradient pass bit for bit — for pred_init, confidence and the gradient of the normalised
+    affinities.  (The raw-affinity gradient then goes through a_ref = 1 - sum a_k, a
+    subtraction: there the bound dominates and is not equal.)"""
+    s = bc.grid_inputs("nonneg")
+    for k in ("pred_init", "grad_pred", "grad_inter"):
+        s[k] = np.abs(s[k])
+    g, x, info = bc.oracle_bound(oracle, "nonneg", s)
+    assert np.array_equal(g["pred_init"], x["pred_init"]) and np.any(g["pred_init"] > 0)
+    assert np.array_equal(g["confidence"], x["confidence"]) and np.any(g["confidence"] > 0)
+    assert np.array_equal(*info["aff_norm"]) and np.any(info["aff_norm"][0] > 0)
+    assert np.all(x["aff"] >= np.abs(g["aff"])) and np.all(x["offset"] >= np.abs(g["offset"]))
+
+
+@pytest.mark.parametrize("name", list(bc.CASES))
+def test_reference_float32_meets_bar(oracle, name):
+    """The reference's own arithmetic in sequential float32 (its forward is bit-equal to the
+    kernels') against float64, per element and relative to the magnitude bound (the affinity
+    gradient less its per-element tanh allowance, _bwd_cases.aff_slack): no worse than the tabled
+    R32, and R32 under the derived ceiling."""
+    _, g64, x, info, g32, _ = _run(oracle, name)
+    assert set(bc.R32[name]) == set(bc.tensors_of(name))
+    for t in bc.tensors_of(name):
+        r, zeros_ok, _ = bc.ratio(g32[t], g64[t], x[t], bc.checked_mask(name, t, g32[t]),
+                                  bc.aff_slack(name, info) if t == "aff" else 0.0)
+        print(f"r32 {name} {t} {r:.3e}")
+        assert zeros_ok, t
+        assert r <= bc.R32[name][t], (t, r)
+        assert bc.R32[name][t] <= bc.ceiling(name, t), (t, bc.R32[name][t], bc.ceiling(name, t))
+
+
+@pytest.mark.parametrize("i", range(6))
+def test_dcn_bound_and_float32_bar(oracle, i):
+    case = bc.dcn_cases()[i]
+    inp, wt, _, off, mask, go = bc.dcn_inputs(100 + i, *case)
+    geom = [case[6], case[7], case[8], case[2], case[3]]  # stride, pad, dilation, group, deformable group
+    args = lambda d: [a.astype(d) for a in (inp, wt, off, mask, go)] + geom  # noqa: E731
+    g64, x = oracle.mdcn_backward_bound(*args(np.float64))
+    g32, _ = oracle.mdcn_backward_bound(*args(np.float32))
+    ref = oracle.mdcn_backward(*args(np.float64))
+    for t, a32, a64, xa, r64 in zip(bc.DCN_TENSORS, g32, g64, x, ref):
+        assert np.array_equal(a64, r64), t
+        assert np.all(xa >= np.abs(a64)), t
+        r, zeros_ok, _ = bc.ratio(a32, a64, xa)
+        print(f"dcn r32 {i} {t} {r:.3e}")
+        assert zeros_ok and r <= bc.DCN_R32[i][t] <= bc.dcn_ceiling(case, t), (t, r)

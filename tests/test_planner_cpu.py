@@ -59,3 +59,25 @@ def test_plans_match_table(plans, golden, kind):
     for got, want in zip(plans[kind], golden[kind]):
         assert got == want, (want["name"], {k: (got.get(k), want.get(k)) for k in set(got) | set(want)
                                             if got.get(k) != want.get(k)})
+
+
+# The per-element backward cases (tests/_bwd_cases.py, tests/test_gpu_backward_elem.py) select the
+# backward's forms by shape alone; a planner change must not move them silently.  At the MI355X's
+# 256 CUs: what each case is named for.
+BWD_FORMS = {
+    "res_tiny_parts": ("resident", 120, 1), "res_far": ("resident", 128, 1),
+    "res_one_part": ("resident", 1, 3), "res_two_parts": ("resident", 2, 2),
+    "res_T2": ("resident", 128, 1), "res_T24": ("resident", 128, 1), "res_odd": ("resident", 84, 1),
+    "res_noconf": ("resident", 120, 1), "res_nopreserve": ("resident", 120, 1),
+    "res_AS": ("resident", 120, 1), "res_ASS": ("resident", 120, 1), "res_TC": ("resident", 120, 1),
+    "steps_split_clip": "steps", "steps_split_manyB": "steps",
+    "onepass_longT": "onepass", "onepass_env": "onepass", "k17": "onepass", "k5x5": "onepass", "k7x7": "onepass",
+    "noffset": "onepass", "range": ("resident", 128, 1), "nonexact": ("resident", 120, 1),
+}
+
+
+def test_backward_cases_select_their_forms(tmp_path):
+    import _bwd_cases as bc
+    got = {n: bc.backward_form(n, 256, str(tmp_path)) for n in bc.CASES if bc.CASES[n]["form"] == "fused"}
+    assert got == BWD_FORMS, {n: (got.get(n), BWD_FORMS.get(n)) for n in set(got) | set(BWD_FORMS)
+                              if got.get(n) != BWD_FORMS.get(n)}
