@@ -371,6 +371,17 @@ int nlspn_resident_config(int dtype, int B, int H, int W, int kh, int kw, int T,
                           int *grid, int *block, int *lds_bytes);
 
 /*
+ * Diagnostics: 1 if the resident launches of an nlspn_propagate call of this shape
+ * (16-B aligned planes, raw offsets, a workspace; off_out given iff has_off_out) carry
+ * the helper wave that copies the output dict's inserted offsets (one wave behind the
+ * quad-owning threads nlspn_resident_config reports; NLSPN_RES_HELPER=0 in the
+ * environment keeps the main waves' copy), 0 otherwise.  *block (optional): the
+ * threads per workgroup the first resident launch is given, 0 without a resident plan.
+ */
+int nlspn_resident_helper(int dtype, int B, int H, int W, int kh, int kw, int T, int has_conf,
+                          int has_off_out, int *block);
+
+/*
  * Sticky abort status of the resident path on the current device: 1 if a resident
  * launch aborted since the last clear (a part polled past its spin limit, i.e. the
  * grid was not co-resident — e.g. a concurrent resident launch from another

@@ -73,6 +73,7 @@ SIGNATURES = {
     "nlspn_time_propagate": (_i, [_i, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _i, _i, _i, _i, _i, _i, _i, _u, _i, _vp, _vp, _vp, _vp]),
     "nlspn_resident_config": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "nlspn_resident_helper": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "nlspn_resident_status": (_i, [_i]),
     "nlspn_affinity_normalize_backward": (_i, [_i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "nlspn_gconv_pack_layout": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
@@ -97,8 +98,8 @@ SIGNATURES = {
 
 # Entry points an A/B build (NLSPN_LIB_PATH) of an earlier round may lack; any other
 # missing symbol fails the load (a stale or wrong library is refused up front)
-AB_OPTIONAL = frozenset({"nlspn_resident_status", "nlspn_resident_config", "nlspn_gconv_pack_layout", "nlspn_gconv",
-                         "nlspn_gconv_affnorm", "nlspn_gconv_dgrad", "nlspn_gconv_wgrad_workspace_bytes",
+AB_OPTIONAL = frozenset({"nlspn_resident_status", "nlspn_resident_config", "nlspn_resident_helper",
+                         "nlspn_gconv_pack_layout", "nlspn_gconv", "nlspn_gconv_affnorm", "nlspn_gconv_dgrad", "nlspn_gconv_wgrad_workspace_bytes",
                          "nlspn_gconv_wgrad", "nlspn_gconv_gru_train", "nlspn_gconv_gru_gates_backward",
                          "nlspn_gconv16_pack_layout", "nlspn_gconv16",
                          "nlspn_gconv_wgrad_bf16x3_workspace_bytes", "nlspn_gconv_wgrad_bf16x3"})

@@ -55,6 +55,7 @@ Switches read_switches() {
     sw.res_merge = !env_is("NLSPN_RES_MERGE", '0');
     sw.res_l2 = !env_is("NLSPN_RES_L2", '0');
     sw.res_offcopy = !env_is("NLSPN_RES_OFFCOPY", '0');
+    sw.res_helper = !env_is("NLSPN_RES_HELPER", '0');
     if (const char *gs = getenv("NLSPN_RES_GRID"))  // "gy,gx" or "gyxgx"
         if (sscanf(gs, "%d%*c%d", &sw.res_gy, &sw.res_gx) != 2) sw.res_gy = sw.res_gx = 0;
     sw.res_dbg = env_dbg("NLSPN_RES_DBG");

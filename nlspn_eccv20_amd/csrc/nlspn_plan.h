@@ -29,6 +29,7 @@ struct Switches {
     bool res_merge = true;     // NLSPN_RES_MERGE=0: one launch per image group
     bool res_l2 = true;        // NLSPN_RES_L2=0: every hand-off line exported (write-through)
     bool res_offcopy = true;   // NLSPN_RES_OFFCOPY=0: step 1 writes the inserted offsets
+    bool res_helper = true;    // NLSPN_RES_HELPER=0: the main waves copy them in the loop, no helper wave
     int res_gy = 0, res_gx = 0;  // NLSPN_RES_GRID="gy,gx": the part grid (same images per launch)
     unsigned res_dbg = 0;      // NLSPN_RES_DBG (experiments build only, nlspn_common.h kExperiments)
 };

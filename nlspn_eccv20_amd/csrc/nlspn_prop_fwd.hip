@@ -189,6 +189,9 @@ void res_query(const ResInputs &in, const Switches &sw, ResPlanRec &R) {
                   !(in.flags & kResOffInserted);
 }
 
+// where a resident launch copies the inserted offsets to (its main waves or its helper wave), or null
+void *res_off_dst(const ResArgs &a) { return a.off_out ? a.off_out : a.off_out_h; }
+
 // Step 3 of the plan, the arguments: ResArgs per image group, then the merged launch.
 void res_fill_args(const ResInputs &in, int B, int H, int W, int K, int T, const Switches &sw, ResPlan &P) {
     const ResPlanRec &R = P.rec;
@@ -207,6 +210,21 @@ void res_fill_args(const ResInputs &in, int B, int H, int W, int K, int T, const
     // the output dict's inserted offsets copied by the resident loop (ResArgs::off_out)
     // instead of step 1; NLSPN_RES_OFFCOPY=0 (A/B) leaves them to step 1
     const bool copy_off = in.off_out && ((!(in.flags & kResOffInserted) && sw.res_offcopy && aligned(in.off_out, vb)) || R.first);
+    // ... by a helper wave (kResHelper: the launch has S.nt + 64 threads) in the builds that copy
+    // in the loop (ntc: the build's compile-time thread count; the 128-thread and split-quad
+    // builds copy in their setup), where the launch bound has room for the wave;
+    // NLSPN_RES_HELPER=0 (A/B) keeps the main waves' copy
+    const auto helper = [&](int ntc) {
+        return copy_off && sw.res_helper && ntc != 128 && !R.split && S.nt % 64 == 0 && S.nt + 64 <= kResMaxNT;
+    };
+    // the destination goes to the copying waves' field: off_out (the main waves') or off_out_h
+    // (the helper's, with the flag); the other stays null
+    const auto set_copy = [&](ResArgs &a, void *dst, int ntc) {
+        const bool h = helper(ntc);
+        a.flags = (a.flags & ~kResHelper) | (h ? kResHelper : 0u);
+        a.off_out = h ? nullptr : dst;
+        a.off_out_h = h ? dst : nullptr;
+    };
     for (int k = 0; k < R.ngroups; ++k) {
         const long long b0 = (long long)k * S.Bg;
         auto at = [&](const void *p, long long elems) -> const void * {
@@ -219,7 +237,7 @@ void res_fill_args(const ResInputs &in, int B, int H, int W, int K, int T, const
                          static_cast<unsigned *>(in.workspace), ds ? ds->dev_status : nullptr, in.off_bs,
                          (long long)B * HW, (int)std::min<long long>(S.Bg, B - b0), H, W, T, S.gy, S.gx, S.win_cells,
                          (unsigned)(k * (T + 1)), in.flags | (l2ok ? kResL2 : 0u), sw.res_dbg};
-        if (copy_off) P.a[k].off_out = const_cast<void *>(at(in.off_out, b0 * 2 * (K + 1) * HW));
+        if (copy_off) set_copy(P.a[k], const_cast<void *>(at(in.off_out, b0 * 2 * (K + 1) * HW)), R.ntc);
         if (R.first) {  // the prologue in the launch: raw inputs, conf' written here (read back by the rim staging)
             P.a[k].flags |= kResFirst;
             P.a[k].conf = at(in.conf_out, b0 * HW);
@@ -236,9 +254,10 @@ void res_fill_args(const ResInputs &in, int B, int H, int W, int K, int T, const
     // (every merged shape has a GROUPS build; should one be missing, the groups launch
     // one by one rather than a single-group build running only group 0)
     if (!R.merged || !P.fn_merged) return;
-    P.a[0].ngroups = R.nfull;
     P.nlaunch = 1;
     if (R.ngroups > R.nfull) P.a[P.nlaunch++] = P.a[R.ngroups - 1];  // the partial group, launched after the merged one
+    P.a[0].ngroups = R.nfull;
+    if (copy_off) set_copy(P.a[0], res_off_dst(P.a[0]), R.ntc_merged);  // (the merged launch's build)
 }
 
 // Fills P and returns true when the resident kernel applies (iterations 2..T).
@@ -281,7 +300,9 @@ int launch_resident(ResPlan &P, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent
     for (int k = 0; k < P.nlaunch; ++k) {
         const void *fn = k == 0 && P.fn_merged ? P.fn_merged : P.fn;
         const unsigned grid = (unsigned)(P.a[k].B * P.a[k].gy * P.a[k].gx);  // a part per workgroup
-        NLSPN_TRY(launch_section(LaunchRec{fn, dim3(grid), dim3((unsigned)P.rec.S.nt), P.rec.lds, true, StepArgs{}, P.a[k]},
+        // (kResHelper: the helper wave behind the S.nt quad-owning threads)
+        const unsigned block = (unsigned)P.rec.S.nt + ((P.a[k].flags & kResHelper) ? 64u : 0u);
+        NLSPN_TRY(launch_section(LaunchRec{fn, dim3(grid), dim3(block), P.rec.lds, true, StepArgs{}, P.a[k]},
                                  s, k == 0 ? e0 : nullptr, k == P.nlaunch - 1 ? e1 : nullptr));
     }
     return NLSPN_OK;
@@ -373,7 +394,7 @@ int propagate_impl(int dtype, const void *pred_init, const void *dep, const void
         if (resident) *resident = P.nlaunch | kResidentFirstBit;
         return launch_resident(P, s, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr);
     }
-    if (res && P.a[0].off_out) r1.a.off_out = nullptr;  // the resident loop copies the offsets
+    if (res && res_off_dst(P.a[0])) r1.a.off_out = nullptr;  // the resident loop copies the offsets
     if (res) arm_resident(r1.a, P, pred_inter, N, es, T);
     NLSPN_TRY(launch(L1, r1.a, s, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
     if (res) {
@@ -595,6 +616,25 @@ int nlspn_resident_config(int dtype, int B, int H, int W, int kh, int kw, int T,
     if (block) *block = P.rec.S.nt;
     if (lds_bytes) *lds_bytes = (int)P.rec.lds;
     return 1;
+}
+
+int nlspn_resident_helper(int dtype, int B, int H, int W, int kh, int kw, int T, int has_conf, int has_off_out,
+                          int *block) {
+    // the plan of an nlspn_propagate call with aligned tensors and raw offsets
+    if (block) *block = 0;
+    ResPlan P;
+    alignas(16) static char dummy[16];
+    void *d = dummy;
+    ResInputs in{dtype, has_conf ? d : nullptr, d, d, d, 2LL * (kh * kw - 1) * H * W, d, d, d, NLSPN_PRESERVE_INPUT,
+                 has_off_out ? d : nullptr};
+    in.has_first = true;
+    in.pinit = d; in.conf_raw = has_conf ? d : nullptr; in.aff_raw = d; in.aff_bs = (long long)(kh * kw - 1) * H * W;
+    alignas(16) static const float gamma = 1.f;
+    in.gamma = &gamma; in.aff_out = d; in.conf_out = has_conf ? d : nullptr;
+    if (!plan_resident(in, B, H, W, kh, kw, T, P)) return 0;
+    const bool helper = (P.a[0].flags & kResHelper) != 0;
+    if (block) *block = P.rec.S.nt + (helper ? 64 : 0);
+    return helper ? 1 : 0;
 }
 
 int nlspn_resident_status(int clear) {

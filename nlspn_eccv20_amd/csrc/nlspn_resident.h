@@ -118,6 +118,10 @@ struct ResArgs {
     void *aff_out;
     long long aff_bs;
     int kind;
+    // With flags kResHelper the inserted offsets' destination is here and `off_out` is null:
+    // the main waves then run the code of a launch that copies nothing (a flag tested in their
+    // loop cost every iteration a kernarg re-load and its wait), and the helper wave copies.
+    void *off_out_h;
 };
 
 typedef const __attribute__((address_space(4))) ResArgs ResArgsK;  // the kernarg segment's ResArgs
@@ -141,6 +145,10 @@ constexpr unsigned kSc1 = 16u;                   // buffer-instruction aux bit: 
 constexpr unsigned kResOffInserted = 0x100u;      // ResArgs::flags: offsets in the inserted 2(K+1)-plane layout
 constexpr unsigned kResL2 = 0x400u;               // ResArgs::flags: same-XCD hand-offs may stay in the XCD's L2
 constexpr unsigned kResFirst = 0x800u;            // ResArgs::flags: the prologue and iteration 1 in the launch
+// ResArgs::flags: the launch has NT + 64 threads; the last wave (tid >= NT) owns no quad and no
+// LDS row and copies the inserted offsets (ResArgs::off_out) in place of the main waves' loop
+// copy (res_helper_group).  Set by the host only for the builds that copy in the loop.
+constexpr unsigned kResHelper = 0x1000u;
 // "not yet written" values of the handed-off planes (nlspn_step.h kPoison32 / kPoison16,
 // also stored by step 1): signalling NaNs (quiet bit clear), which no arithmetic result is
 // (an instruction returns a NaN quieted), so a computed p_t never equals them
@@ -384,6 +392,90 @@ template <int PX> __device__ __forceinline__ void win_put(float *fwin, float *fw
     }
 }
 
+// The helper wave of a part (ResArgs::flags kResHelper: the wave with tid >= NT), one image
+// group: it copies the part's own quads of the output dict's inserted offsets (ResArgs::off_out,
+// 2(K+1) planes: the raw planes with the reference tap's two zero planes inserted), one plane
+// per iteration, in place of the main waves' loop copy (ResArgs::off_out_h): the main waves
+// then spend no issue slots of their critical path on it.  Plane c + 1 is loaded as soon as
+// plane c is stored, so it has a whole iteration to arrive.  The wave owns no quad and no LDS row: of LDS it only reads the abort
+// word.  It executes exactly the main waves' barriers of a group — the setup's four, the
+// prologue form's publish barrier, iteration 1's export-list barrier, and per iteration the
+// staging barrier (with the abort check behind it) and the post-tap barrier; the caller shares
+// the abort path's and the exit's.  MR: rounds of 64 quads that cover a part's quads.
+// Returns the iteration the part aborted at (0: none), as the main waves' t_abort.
+template <typename T, int K, int MR, bool FIRST>
+__device__ __forceinline__ int res_helper_group(ResArgsK &a, const int *ctl, int b, int r0, int c0, int nqw,
+                                                int nownq, int lane, unsigned wbase) {
+    constexpr int REF = K / 2, NP = 2 * (K + 1);
+    constexpr unsigned ES = sizeof(T);
+    const long long HW = (long long)a.H * a.W;
+    const unsigned plane_bytes = (unsigned)HW * ES;
+    const bool on = a.off_out_h != nullptr;
+    const rsrc_t ro = make_rsrc(static_cast<const T *>(a.off) + (long long)b * a.off_bs);
+    const rsrc_t rco = make_rsrc(static_cast<T *>(a.off_out_h) + (long long)b * NP * HW);
+    unsigned vo[MR];  // byte offset of quad lane + 64 i of the part (row-major) in a plane
+#pragma unroll
+    for (int i = 0; i < MR; ++i) {
+        const int q = lane + 64 * i < nownq ? lane + 64 * i : 0, rr = q / nqw;
+        vo[i] = (unsigned)((r0 + rr) * a.W + 4 * (c0 + q - rr * nqw)) * ES;
+    }
+    float v[MR][4];
+    // output plane c: raw plane 2 k + (c & 1) of tap c / 2 (k skips the reference tap), or zero
+    const auto load = [&](const int c) {
+        const int tt = c >> 1, src = tt == REF ? -1 : 2 * (tt < REF ? tt : tt - 1) + (c & 1);
+#pragma unroll
+        for (int i = 0; i < MR; ++i) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[i][e] = 0.f;
+            if (src >= 0 && lane + 64 * i < nownq) ResVec<T>::template load<0>(ro, vo[i], (unsigned)src * plane_bytes, v[i]);
+        }
+    };
+    const auto store = [&](const int c) {  // streaming (nt): an output only
+#pragma unroll
+        for (int i = 0; i < MR; ++i)
+            if (lane + 64 * i < nownq) ResVec<T>::template store<kNT>(rco, vo[i], (unsigned)c * plane_bytes, v[i]);
+    };
+    const bool wtrace = kResWTrace && (exp_dbg(a.dbg) & 8u) && lane == 0;
+    if (wtrace) {  // (row 0: the wave's HW_ID, as the main waves')
+        unsigned hw;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        res_wtrace(a.pred, a.T, wbase, -1)[0] = hw;
+    }
+    lds_barrier();  // the setup's: the control words,
+    lds_barrier();  // the span merge,
+    lds_barrier();  // the window words,
+    lds_barrier();  // the window zeroed
+    if (FIRST) lds_barrier();  // the prologue form's, before the part publishes
+    if (on) load(0);
+    const int t0 = FIRST ? 0 : 1;
+    int t_abort = 0;
+    for (int t = t0; t < a.T; ++t) {
+        if (t == 1) lds_barrier();  // the export list
+        lds_barrier();              // staging done
+        if (ctl[0]) {
+            t_abort = t;
+            break;
+        }
+        const int c = t - t0;
+        if (on && c < NP) {
+            store(c);
+            if (t == a.T - 1) {  // a short section: the planes past T - 1, here
+                for (int c2 = c + 1; c2 < NP; ++c2) {
+                    load(c2);
+                    store(c2);
+                }
+            } else if (c + 1 < NP) {
+                load(c + 1);
+            }
+        }
+        // trace: the wave's arrival at the post-tap barrier (the main waves' "taps + stores
+        // issued"; its stores are not waited for: both stamps)
+        if (wtrace) res_wtrace(a.pred, a.T, wbase, t)[0] = res_wtrace(a.pred, a.T, wbase, t)[1] = __builtin_amdgcn_s_memrealtime();
+        lds_barrier();  // taps done
+    }
+    return t_abort;
+}
+
 // 3x3 geometry (K = 8, prop_kernel 3, the reference default), raw offset layout.
 // MAXNT = launch bound (threads), SMAX = staging quads per thread per round.
 // NTC = the thread count as a compile-time constant (0: blockDim.x at run time).
@@ -408,7 +500,8 @@ __global__ void __launch_bounds__(MAXNT) prop_resident_kernel(ResArgs a) {
     // (s[rx], s[rx+1]) is ONE 8-byte-aligned ds_read_b64 from one of the copies
     // With a compile-time thread count the window size is one too (res_win_cells),
     // so every fwinB access is an immediate offset from its fwin address.
-    const int NT = NTC ? NTC : (int)blockDim.x;
+    // (kResHelper: the launch has one more wave, which owns no quad, below)
+    const int NT = NTC ? NTC : (int)blockDim.x - ((a.flags & kResHelper) ? 64 : 0);
     const int WC = NTC ? res_build_cells(NTC, NTC, K, PX) : a.win_cells;
     // PITCH: the window's row pitch as a compile-time constant (576-thread builds: the
     // second footprint row is a ds_read immediate offset, and the window cells are kept as
@@ -459,6 +552,20 @@ __global__ void __launch_bounds__(MAXNT) prop_resident_kernel(ResArgs a) {
     const long long HW = (long long)H * W;
     const unsigned plane_bytes = (unsigned)HW * ES;
     const int b = bl + grp * a.B;
+
+    // ---- the helper wave (kResHelper): the inserted-offset copy and the part's barriers, nothing
+    // else of the group (wave-uniform: NT is a multiple of 64)
+    if ((a.flags & kResHelper) && __builtin_amdgcn_readfirstlane(tid) >= NT) {
+        constexpr int MR = ((NTC ? NTC : MAXNT - 64) / TPQ + 63) / 64;
+        const int ta = res_helper_group<T, K, MR, FIRST>(a, ctl, b, r0, c0, nqw, nownq, lane,
+                                                         (unsigned)__builtin_amdgcn_readfirstlane(tid & ~63));
+        if (ta) {
+            lds_barrier();  // the abort path's (res_finish: wave 0 only)
+            return;
+        }
+        if (!GROUPS || grp + 1 >= ngroups) break;
+        continue;
+    }
 
     // ---- own quad and its invariants.  Taps are held as their sample coordinates
     // (h_im, w_im) = (y - PH + i + dh, x - PW + j + dw), the reference's own
@@ -891,7 +998,12 @@ __global__ void __launch_bounds__(MAXNT) prop_resident_kernel(ResArgs a) {
         // 9 % (C3) per section against no copy at all (timing builds, profiles/r05/
         // ab_offcopy_cost_*.txt); stored by the setup instead it costs 8 % / 6 % more, and with
         // its load sent straight to LDS (global_load_lds, no registers held) 1 % / 2 % more
-        // (ab_offcopy_dma_*.txt): it is traffic beside the hand-offs, not register pressure
+        // (ab_offcopy_dma_*.txt).  With kResHelper the helper wave copies instead
+        // (res_helper_group; off_out is then null here, so no flag is tested in this loop): that
+        // takes the copy's issue work off these waves (C2 1.5 %, C3 1.3 %, C5 4.4 % per step)
+        // but does not shorten the staging wait (traces, profiles/r07): the rest of the 5 % /
+        // 9 % is the copy's traffic beside the hand-offs.  This form stays as the A/B baseline
+        // (NLSPN_RES_HELPER=0) and for parts that need every thread the launch bound allows
         const int cpc = t - t0;
         const bool cpy = !OFFSETUP && a.off_out != nullptr && cpc < 2 * (K + 1);
         const int cptt = cpc >> 1;
