@@ -175,3 +175,151 @@ def test_backward_unit_compiles_without_scratch(tmp_path):
     bad = {n: (r.get("ScratchSize"), r.get("VGPRs Spill")) for n, r in rows.items()
            if r.get("ScratchSize", 0) != 0 or r.get("VGPRs Spill", 0) != 0}
     assert not bad, bad
+
+
+# ------------------------------------------------------------------ the per-element cases (tests/_gconv_bwd_cases.py)
+import _gconv_bwd_cases as bc  # noqa: E402
+
+DG_IDS = [c["id"] for c in bc.DG_CASES]
+GW_IDS = [c["id"] for c in bc.GW_CASES]
+GATE_IDS = [c["id"] for c in bc.GATE_CASES]
+
+
+@pytest.mark.parametrize("cid", ["dg32-2x128>64-6x41-off1.1", "dg33-2x32>16-6x41-off0.1", "dg34-2x64>128-6x41-off1.7",
+                                 "dg35-2x8>16-6x41-off7.0", "dg36-2x128>128-5x38"])
+def test_dgrad_reference_is_the_input_gradient_of_the_torch_module(cid):
+    """The float64 reference of each preset kind against the module the model holds: a stride-2
+    Conv2d (presets 32 / 33), a ConvTranspose2d whose output is cropped (34 / 35), a stride-1
+    Conv2d (36), each with a bias (which the gradient must not see)."""
+    c, o = bc.DG_BY_ID[cid], bc.dgrad_operands(cid)
+    if c["mode"] == bc.S2:
+        mod = torch.nn.ConvTranspose2d(c["cout"], c["cg"], 3, 2, 1, 1)
+    else:
+        mod = torch.nn.Conv2d(c["cout"], c["cg"], 3, 2 if c["mode"] == bc.T2 else 1, 1)
+    mod = mod.double()
+    with torch.no_grad():
+        mod.weight.copy_(o["w"])
+    x = torch.randn((c["B"], c["cout"], c["Ho"], c["Wo"]), dtype=torch.float64, requires_grad=True)
+    y = mod(x)[..., :c["Hg"], :c["Wg"]]
+    (y * o["g"].double()).sum().backward()
+    ref = bc.dgrad_linear(c, o["g"].double(), o["w"].double())
+    assert float(x.grad.abs().max()) > 0.1
+    assert torch.allclose(ref, x.grad, rtol=1e-12, atol=1e-12 * float(x.grad.abs().max()))
+
+
+@pytest.mark.parametrize("cid", DG_IDS)
+def test_dgrad_bound_dominates_and_float32_is_within_a_quarter_of_the_bar(cid):
+    """X >= |ref| everywhere, and R32: torch's float32 evaluation of the same operation on the
+    CPU is within c / 4 of the float64 reference at every element (tanh: beside e)."""
+    R = bc.dgrad_reference(cid)
+    assert bool((R["X"] * (1 + 1e-12) >= R["ref"].abs()).all())
+    assert bool(torch.isfinite(R["ref"]).all()) and float(R["c"].max()) <= bc.C_MFMA
+    got = bc.dgrad_float32(cid).double()
+    assert bool(((got - R["ref"]).abs() <= 0.25 * R["c"] * R["X"] + R["e"]).all()), bc.ratio(got, R["ref"], R["X"], R["e"])
+
+
+@pytest.mark.parametrize("cid", ["dg32-2x128>64-7x21-off1.0-relu-add.sep", "dg34-2x64>128-7x21-off1.0-relu-add.sep",
+                                 "dg36-2x128>128-7x21-relu-scale0.1-add.sep", "dg35-2x8>16-6x41-off1.7"])
+def test_dgrad_bound_is_the_gradient_when_nothing_is_negative(cid):
+    R = bc.dgrad_reference(cid, "nonneg")
+    assert float(R["ref"].max()) > 1 and torch.allclose(R["ref"], R["X"], rtol=1e-14, atol=0)
+
+
+@pytest.mark.parametrize("cid", ["dg34-2x64>128-6x41-off1.7", "dg35-2x8>16-6x41-off7.0", "dg34-2x64>128-6x41-off7.7"])
+def test_cropped_gradient_reference_is_the_uncropped_one_with_zero_rows(cid):
+    c, o = bc.DG_BY_ID[cid], bc.dgrad_operands(cid)
+    full = dict(c, Hg=2 * c["Ho"], Wg=2 * c["Wo"])
+    gz = torch.zeros((c["B"], c["cg"], full["Hg"], full["Wg"]), dtype=torch.float64)
+    gz[..., :c["Hg"], :c["Wg"]] = o["g"]
+    a, b = bc.dgrad_linear(c, o["g"].double(), o["w"].double()), bc.dgrad_linear(full, gz, o["w"].double())
+    assert c["Hg"] < full["Hg"] or c["Wg"] < full["Wg"]
+    assert torch.allclose(a, b, rtol=1e-12, atol=1e-13)
+
+
+@pytest.mark.parametrize("cid", GW_IDS)
+def test_wgrad_plan_mirror_bound_and_float32_condition(cid):
+    """The mirror's workspace equals the library's query (no device), the case hits the edges
+    its id claims, X >= |ref|, and R32 for dW and db."""
+    c = bc.GW_BY_ID[cid]
+    p = bc.gw_plan_of(c)
+    need = _lib.get().nlspn_gconv_wgrad_workspace_bytes(c["stride"], c["Cs"], c["c0"] + c["c1"], c["B"], c["Hs"], c["Ws"],
+                                                        c["Hl"], c["Wl"])
+    assert need == 4 * p["floats"] > 0
+    assert c["edges"] <= bc.gw_edges(p), (c["edges"] - bc.gw_edges(p), p)
+    if c["stride"] == 2:  # the large size from {2 Hs, 2 Hs - 1, 2 Hs - 7} x {2 Ws, 2 Ws - 1, 2 Ws - 7}
+        assert 2 * c["Hs"] - c["Hl"] in (0, 1, 7) and 2 * c["Ws"] - c["Wl"] in (0, 1, 7)
+    assert c["c1"] == 0 or (c["c0"] % 16 == 0 and not c["bfl"])
+    R = bc.wgrad_case_reference(cid)
+    assert bool((R["Xw"] * (1 + 1e-12) >= R["dw"].abs()).all()) and bool((R["Xb"] * (1 + 1e-12) >= R["db"].abs()).all())
+    dw32, db32 = bc.wgrad_float32(cid)
+    assert bool(((dw32.double() - R["dw"]).abs() <= 0.25 * R["cw"] * R["Xw"]).all()), bc.ratio(dw32, R["dw"], R["Xw"])
+    assert bool(((db32.double() - R["db"]).abs() <= 0.25 * R["cb"] * R["Xb"]).all()), bc.ratio(db32, R["db"], R["Xb"])
+
+
+def test_wgrad_cases_cover_every_tiling_and_edge():
+    by = {}
+    for c in bc.GW_CASES:
+        e = bc.gw_edges(bc.gw_plan_of(c))
+        by.setdefault(next(x for x in e if x.startswith("tiling")), set()).update(e)
+        assert c["Ws"] in (1, 3, 13, 18, 36, 48, 64, 65, 130)
+    assert set(by) == {"tiling1222", "tiling2222", "tiling2241", "tiling2111"}
+    for t, e in by.items():
+        assert {"bands1", "bands2", "bands3", "units1", "last_slice_short", "padded_kstep"} <= e, (t, e)
+    assert any(c["Hs"] == 1 for c in bc.GW_CASES) and {c["scale"] for c in bc.GW_CASES} == {1.0, 0.1}
+    assert {(c["bfl"], bc.gw_plan_of(c)["nsb"] > 1) for c in bc.GW_CASES} == {(False, False), (False, True), (True, False), (True, True)}
+    # three bands of 130: 44 | 44 | 42, the last one's k-steps padded to 44; two bands of 65: 33 | 32
+    assert bc.gw_plan(1, 24, 40, 1, 2, 130, 2, 130)["widths"] == [44, 44, 42] and bc.gw_plan(1, 24, 40, 1, 2, 130, 2, 130)["k4"][-1] == 44
+    assert bc.gw_plan(1, 40, 48, 2, 3, 65, 3, 65)["widths"] == [33, 32]
+
+
+@pytest.mark.parametrize("cid", DG_IDS)
+def test_dgrad_case_hits_its_claimed_edge(cid):
+    c = bc.DG_BY_ID[cid]
+    assert c["edges"] <= bc.dg_edges(c["preset"], c["gh"], c["gw"]), (c["edges"], bc.dg_edges(c["preset"], c["gh"], c["gw"]))
+    if c["mode"] == bc.T2:
+        assert (c["Hg"], c["Wg"]) == (c["gh"], c["gw"]) and 2 * c["Hg"] - c["Ho"] in (0, 1) and 2 * c["Wg"] - c["Wo"] in (0, 1)
+    elif c["mode"] == bc.S2:
+        assert (c["Ho"], c["Wo"]) == (c["gh"], c["gw"]) and 0 <= 2 * c["Ho"] - c["Hg"] <= 7 and 0 <= 2 * c["Wo"] - c["Wg"] <= 7
+    assert c["cg"] * c["Hg"] * c["Wg"] <= 256 * 17 * 39 * 4 and c["cout"] <= 256
+
+
+def test_dgrad_grids_are_the_forward_tests_and_the_s1_empty_tile_grid_is_the_smallest():
+    assert {(c["preset"], c["gh"], c["gw"]) for c in bc.DG_A} >= {
+        (32, 17, 39), (32, 3, 43), (33, 27, 160), (33, 4, 129), (34, 14, 23), (34, 4, 33), (35, 17, 37), (35, 3, 43), (36, 17, 39)}
+    empty = [(gh * gw, gh, gw) for gh in range(1, 24) for gw in range(1, 130) if bc.gc_tiling(*bc.DG_GEO[36], gh, gw)["empty_last"]]
+    assert min(empty)[1:] == (3, 43) and (36, 3, 43) in {(c["preset"], c["gh"], c["gw"]) for c in bc.DG_A}
+    # the mirror's geometry is the library's: the output-channel tile of every data-gradient preset
+    for preset, co in bc.DG_CO_TILE.items():
+        assert G._layout(preset)[0] == co and G._layout(preset)[2] == (bc.DG_GEO[preset][0] == bc.T2)
+
+
+def test_planted_values_survive_the_seeding():
+    for c in bc.DG_CASES:
+        o = bc.dgrad_operands(c["id"])
+        if c["act"] == bc.ACT_RELU:
+            y = o["ysave"].view(-1)
+            assert y[:6].tolist() == list(bc.RELU_PLANTS) and bool(torch.signbit(y[1])) and not bool(torch.signbit(y[0]))
+            assert int((y == 0).sum()) > 6 and int((y < 0).sum()) == 2 and float(y[2]) == 2.0 ** -126
+        elif c["act"] == bc.ACT_TANH:
+            y = o["ysave"].view(-1)
+            assert y[:6].double().tolist() == list(bc.TANH_PLANTS) and float(y.abs().max()) == 1.0 and c["scale"] == 0.1
+        else:
+            assert o["ysave"] is None
+        assert (o["add"] is None) == (c["add"] == "none")
+    o = bc.gate_operands("gates-stage1-3x128x5x7")
+    assert o["z"][-1].view(-1)[:2].tolist() == [0.0, 1.0] and o["r"][-1].view(-1)[:3].tolist() == [0.0, 1.0, 0.5]
+    assert o["q"][-1].view(-1)[:2].tolist() == [1.0, -1.0] and torch.equal(o["q"][-1].view(-1)[5:9], o["h"][-1].view(-1)[5:9])
+    assert (3 * 128 * 5 * 7) % 256 != 0
+    for cid in ("gates-stage0-relu", "gates-stage0-tanh"):
+        y = bc.gate_operands(cid)["z"].view(-1)
+        assert y[:6].double().tolist() == list(bc.RELU_PLANTS if cid.endswith("relu") else bc.TANH_PLANTS)
+    assert bc.SEEDS == {} or all(k in bc.DG_BY_ID or k in bc.GW_BY_ID or k in bc.GATE_BY_ID for k in bc.SEEDS)
+
+
+@pytest.mark.parametrize("cid", GATE_IDS)
+def test_gate_bound_dominates_and_float32_is_within_a_quarter_of_the_bar(cid):
+    want, f32 = bc.gate_formulas(cid, torch.float64), bc.gate_formulas(cid, torch.float32)
+    for k, (ref, X) in want.items():
+        assert bool((X * (1 + 1e-12) >= ref.abs()).all())
+        got = f32[k][0].double()
+        assert bool(((got - ref).abs() <= 0.25 * bc.C_GATES * X).all()), (k, bc.ratio(got, ref, X) / bc.U)
