@@ -8,4 +8,6 @@ namespace nlspn {
 // The 3x3 builds (nlspn_resident.h NLSPN_RES_BUILDS_3X3); the wider geometries' are
 // nlspn_kern_resident_wide.hip.
 NLSPN_RES_BUILDS_3X3(NLSPN_RES_INST)
+// ... and the loop-copy builds without the copy code (NLSPN_RES_NOCOPY_3X3)
+NLSPN_RES_NOCOPY_3X3(NLSPN_RES_INST_NOCOPY)
 }  // namespace nlspn

@@ -6,4 +6,5 @@
 
 namespace nlspn {
 NLSPN_RES_BUILDS_WIDE(NLSPN_RES_INST)
+NLSPN_RES_NOCOPY_WIDE(NLSPN_RES_INST_NOCOPY)
 }  // namespace nlspn

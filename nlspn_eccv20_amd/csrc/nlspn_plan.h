@@ -149,9 +149,10 @@ inline bool res_shape(int B, int H, int W, int kh, int kw, int cus, ResShape &S)
 
 // The plan of a section's resident launches: what the planner needs to know of the call
 // (set by the caller), then what res_plan decides.  The build of a launch is
-// prop_resident_kernel<T, KH, KW, kResMaxNT, kResSMax, NTC, GROUPS, FIRST, PXO> with NTC = ntc
+// prop_resident_kernel<T, KH, KW, kResMaxNT, kResSMax, NTC, GROUPS, FIRST, PXO, COPY> with NTC = ntc
 // (ntc_merged for a merged launch 0, GROUPS = true), FIRST = first, PXO = split;
-// nlspn_prop_fwd.hip maps it to the kernel's address.
+// nlspn_prop_fwd.hip maps it to the kernel's address, and picks COPY per launch (false: the
+// build without the loop's copy code, for main waves that copy nothing).
 struct ResPlanRec {
     int es;  // bytes per element (2 or 4)
     int B, H, W, kh, kw, T;

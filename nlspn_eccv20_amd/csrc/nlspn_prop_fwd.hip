@@ -12,6 +12,8 @@ namespace nlspn {
 // defined in nlspn_kern_resident.hip and nlspn_kern_resident_wide.hip (own translation units)
 NLSPN_RES_BUILDS_3X3(NLSPN_RES_EXTERN)
 NLSPN_RES_BUILDS_WIDE(NLSPN_RES_EXTERN)
+NLSPN_RES_NOCOPY_3X3(NLSPN_RES_EXTERN_NOCOPY)
+NLSPN_RES_NOCOPY_WIDE(NLSPN_RES_EXTERN_NOCOPY)
 }  // namespace nlspn
 
 using namespace nlspn;
@@ -157,15 +159,28 @@ struct ResPlan {
     ResPlanRec rec;
     const void *fn = nullptr;
     const void *fn_merged = nullptr;  // launch 0's kernel when it runs several image groups
+    // the same builds without the loop's copy code (prop_resident_kernel COPY = false), for the
+    // launches whose main waves copy nothing (ResArgs::off_out null); null: the build has one form
+    const void *fn_nc = nullptr, *fn_merged_nc = nullptr;
     int nlaunch = 0;
     int err = 0;  // nonzero: the plan was refused with an error (not a fallback), see nlspn_last_error
     ResArgs a[kResMaxGroups];
 };
 
-// the kernel of a plan's launches (groups: the merged launch 0's), null: no such build
+// the kernel of a plan's launches (groups: the merged launch 0's), null: no such build;
+// nocopy: its form without the loop's copy code (null: the build copies in its setup)
 template <typename T>
-const void *res_kernel(const ResPlanRec &R, bool groups) {
+const void *res_kernel(const ResPlanRec &R, bool groups, bool nocopy = false) {
     const int ntc = groups ? R.ntc_merged : R.ntc;
+    if (nocopy) {
+#define NLSPN_RES_LOOKUP(KH, KW, NTC, G, F)                                  \
+    if (R.kh == KH && ntc == NTC && groups == G && R.first == F && R.split == 0) \
+        return reinterpret_cast<const void *>(&prop_resident_kernel<T, KH, KW, kResMaxNT, kResSMax, NTC, G, F, 0, false>);
+        NLSPN_RES_NOCOPY_3X3(NLSPN_RES_LOOKUP)
+        NLSPN_RES_NOCOPY_WIDE(NLSPN_RES_LOOKUP)
+#undef NLSPN_RES_LOOKUP
+        return nullptr;
+    }
 #define NLSPN_RES_LOOKUP(KH, KW, NTC, G, F, PXO)                                  \
     if (R.kh == KH && ntc == NTC && groups == G && R.first == F && R.split == PXO) \
         return reinterpret_cast<const void *>(&prop_resident_kernel<T, KH, KW, kResMaxNT, kResSMax, NTC, G, F, PXO>);
@@ -271,6 +286,7 @@ bool plan_resident(const ResInputs &in, int B, int H, int W, int kh, int kw, int
     if (!res_plan(device_cus(), sw, R)) return false;
     P.fn = f32 ? res_kernel<float>(R, false) : res_kernel<__half>(R, false);
     if (!P.fn) return false;
+    P.fn_nc = f32 ? res_kernel<float>(R, false, true) : res_kernel<__half>(R, false, true);
     if (sw.res_dbg & 8u) {  // trace stamps (experiments build) go into pred: each launch's part must hold them
         const long long HW = (long long)H * W;
         const long long per = (long long)(T + 1) * (kResWTrace ? 29 : 5) * 8;  // rows: the setup, then one per iteration
@@ -285,6 +301,7 @@ bool plan_resident(const ResInputs &in, int B, int H, int W, int kh, int kw, int
     }
     // the group-loop build for the merged launch; a partial last group keeps the other
     if (R.merged) P.fn_merged = f32 ? res_kernel<float>(R, true) : res_kernel<__half>(R, true);
+    if (R.merged) P.fn_merged_nc = f32 ? res_kernel<float>(R, true, true) : res_kernel<__half>(R, true, true);
     res_fill_args(in, B, H, W, kh * kw - 1, T, sw, P);
     return true;
 }
@@ -295,10 +312,16 @@ bool plan_resident(const ResInputs &in, int B, int H, int W, int kh, int kw, int
 int launch_resident(ResPlan &P, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
     NLSPN_TRY(set_lds_attr(P.fn, (int)P.rec.lds));
     if (P.fn_merged) NLSPN_TRY(set_lds_attr(P.fn_merged, (int)P.rec.lds));
+    if (P.fn_nc) NLSPN_TRY(set_lds_attr(P.fn_nc, (int)P.rec.lds));
+    if (P.fn_merged_nc) NLSPN_TRY(set_lds_attr(P.fn_merged_nc, (int)P.rec.lds));
     if (P.a[0].ngroups > 1 && !P.fn_merged)  // (plan_resident never makes one: a single-group build would run group 0 only)
         return fail(NLSPN_EINVAL, "resident plan: %d merged image groups without a group-loop build", P.a[0].ngroups);
     for (int k = 0; k < P.nlaunch; ++k) {
-        const void *fn = k == 0 && P.fn_merged ? P.fn_merged : P.fn;
+        const bool mg = k == 0 && P.fn_merged;
+        const void *fn = mg ? P.fn_merged : P.fn;
+        // main waves that copy nothing run the build without the copy code
+        const void *nc = mg ? P.fn_merged_nc : P.fn_nc;
+        if (!P.a[k].off_out && nc) fn = nc;
         const unsigned grid = (unsigned)(P.a[k].B * P.a[k].gy * P.a[k].gx);  // a part per workgroup
         // (kResHelper: the helper wave behind the S.nt quad-owning threads)
         const unsigned block = (unsigned)P.rec.S.nt + ((P.a[k].flags & kResHelper) ? 64u : 0u);

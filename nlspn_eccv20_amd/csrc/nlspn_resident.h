@@ -141,7 +141,8 @@ constexpr bool kResGeneralPath = true;
 #else
 constexpr bool kResGeneralPath = false;  // experiment only: wrong results for taps outside the window
 #endif
-constexpr unsigned kSc1 = 16u;                   // buffer-instruction aux bit: sc1 (write-through / L1 bypass)
+constexpr int kResWaitVm0 = 0x0F70;              // s_waitcnt operand (gfx9 encoding): vmcnt(0), the other counters untouched
+constexpr unsigned kSc1 = 16u;                  // buffer-instruction aux bit: sc1 (write-through / L1 bypass)
 constexpr unsigned kResOffInserted = 0x100u;      // ResArgs::flags: offsets in the inserted 2(K+1)-plane layout
 constexpr unsigned kResL2 = 0x400u;               // ResArgs::flags: same-XCD hand-offs may stay in the XCD's L2
 constexpr unsigned kResFirst = 0x800u;            // ResArgs::flags: the prologue and iteration 1 in the launch
@@ -485,8 +486,15 @@ __device__ __forceinline__ int res_helper_group(ResArgsK &a, const int *ctl, int
 // PXO: pixels per thread overriding res_px (0: res_px): small latency-bound parts (a B = 1 NYU
 // image in 247 parts of 72 quads) split a 3x3 quad over two threads, halving each thread's
 // dependency chain of tap-pixel slots.
-template <typename T, int KH, int KW, int MAXNT, int SMAX, int NTC, bool GROUPS, bool FIRST, int PXO = 0>
+// COPY: the iteration loop holds the main waves' inserted-offset copy (run when ResArgs::off_out
+// is set).  COPY = false is the build of a launch whose main waves copy nothing (a helper launch,
+// or no offsets output: off_out null), for the builds that copy in the loop: the same kernel with
+// no copy code in it.  A run-time test of off_out in one loop is not the same thing: the copy's
+// load then stays statically pending in registers the loop reuses, and the compiler's waits for
+// it wait, at run time, for the loop's own stores (below, at the copy).
+template <typename T, int KH, int KW, int MAXNT, int SMAX, int NTC, bool GROUPS, bool FIRST, int PXO = 0, bool COPY = true>
 __global__ void __launch_bounds__(MAXNT) prop_resident_kernel(ResArgs a) {
+    static_assert(COPY || !(NTC == 128 || PXO != 0), "the builds that copy in the setup have one form");
     constexpr int K = KH * KW - 1, REF = K / 2, PH = (KH - 1) / 2, PW = (KW - 1) / 2;
     constexpr int RY = res_ry(KH), RXQ = res_rxq(KW), PADX = kResPadX;
     constexpr int PX = PXO ? PXO : res_px(KH, KW), TPQ = 4 / PX;  // pixels per thread, threads per quad
@@ -631,9 +639,13 @@ __global__ void __launch_bounds__(MAXNT) prop_resident_kernel(ResArgs a) {
         // the normalised (K+1)-plane layout, or with the prologue in the launch the K raw planes
         const rsrc_t ra_ = make_rsrc(static_cast<const T *>(a.aff) + (first ? (long long)b * a.aff_bs : (long long)b * (K + 1) * HW));
         const rsrc_t ro = make_rsrc(static_cast<const T *>(a.off) + (long long)b * a.off_bs);
-        // Issue order (loads return in order): the affinities, dep and conf first — the row
-        // stores and the prologue's normalisation and conf' then run while the 2K offset planes
-        // still stream in — the offsets last (the window pass below waits for them)
+        // Issue order (loads return in order): the affinities, dep and conf first, the offsets
+        // last (the window pass below waits for them), so the row stores and conf' run while the
+        // 2K offset planes still stream in.  The prologue's normalisation does not: as compiled,
+        // its gamma is loaded behind the offset loads and the setup stores, and vmcnt counts in
+        // issue order, so the wait in front of normalize_taps is vmcnt(0).  Loading gamma ahead
+        // of the planes makes it vmcnt(16) and measured no faster ("the loop as
+        // compiled")
 #pragma unroll
         for (int k = 0; k < K; ++k)
             PixVec<T, PX>::template load<0>(ra_, vpix, (unsigned)(first || k < REF ? k : k + 1) * plane_bytes, ak[k]);
@@ -707,7 +719,8 @@ __global__ void __launch_bounds__(MAXNT) prop_resident_kernel(ResArgs a) {
                 row[PX * K] = r1[0];
             }
             // the output dict's `aff` ((K+1) planes, the normalisation's values: fp16 storage
-            // rounds them as step 1 does), streamed now, while the offsets still stream in
+            // rounds them as step 1 does), streamed now, in the setup (the offsets have arrived by
+            // then: the normalisation waited for every load, above)
             // (measured faster than one plane per iteration in the loop: C2 104.6 vs 105.8,
             // C3 223.8 vs 227.9 us per section, profiles/r05)
             if (active) {
@@ -1003,9 +1016,15 @@ __global__ void __launch_bounds__(MAXNT) prop_resident_kernel(ResArgs a) {
         // takes the copy's issue work off these waves (C2 1.5 %, C3 1.3 %, C5 4.4 % per step)
         // but does not shorten the staging wait (traces, profiles/r07): the rest of the 5 % /
         // 9 % is the copy's traffic beside the hand-offs.  This form stays as the A/B baseline
-        // (NLSPN_RES_HELPER=0) and for parts that need every thread the launch bound allows
+        // (NLSPN_RES_HELPER=0) and for parts that need every thread the launch bound allows.
+        // It is the COPY = true form of this loop only.  While one loop held both cases behind a
+        // run-time test of off_out, the copy's load was statically pending in the registers the
+        // poison, the accumulators and the output quad reuse, and the compiler covered it with
+        // s_waitcnt vmcnt(0) at the loop header and right behind the poison store: a launch that
+        // copied nothing waited there for its own stores' acknowledgements ("the
+        // loop as compiled").  The COPY = false form has neither wait.
         const int cpc = t - t0;
-        const bool cpy = !OFFSETUP && a.off_out != nullptr && cpc < 2 * (K + 1);
+        const bool cpy = COPY && !OFFSETUP && a.off_out != nullptr && cpc < 2 * (K + 1);
         const int cptt = cpc >> 1;
         const int cpsrc = cptt == REF ? -1 : 2 * (cptt < REF ? cptt : cptt - 1) + (cpc & 1);
         float cpq[PX];
@@ -1049,6 +1068,12 @@ __global__ void __launch_bounds__(MAXNT) prop_resident_kernel(ResArgs a) {
                     if (l2try && !fail) {  // (the window words were acknowledged before the tag)
                         const unsigned w0 = __hip_atomic_load(wp + 1 + 2 * (grp & 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         const unsigned w1 = __hip_atomic_load(wp + 2 + 2 * (grp & 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        // both words arrive here, on every lane.  They are consumed under the
+                        // lane mask of `cand` only, so on the path where no lane is a candidate
+                        // they stayed statically pending, and the compiler covered them with
+                        // vmcnt(0) waits in every iteration (in front of the poison and in the
+                        // staging loop), which at run time waited for the stores
+                        __builtin_amdgcn_s_waitcnt(kResWaitVm0);
                         const bool cand = jj < nparts && (v & 31u) != xcc_self && (int)(w0 & 0xffffu) <= er1 &&
                                           (int)(w0 >> 16) >= er0 && (int)(w1 & 0xffffu) <= ec1 && (int)(w1 >> 16) >= ec0;
                         const unsigned long long m = __builtin_amdgcn_ballot_w64(cand);
@@ -1200,7 +1225,10 @@ __global__ void __launch_bounds__(MAXNT) prop_resident_kernel(ResArgs a) {
         const bool refull = __builtin_amdgcn_readfirstlane(ctl[6 + (t & 1)]) != 0;
         T *p_out = p_out_all + (size_t)t * a.tstride + b * HW;
         // plane t + 1 is read by iteration t + 2 (if any): its own quad poisoned now, the
-        // store acknowledged before plane t's store below (the hand-off's ordering)
+        // store acknowledged before plane t's store below (the hand-off's ordering).  As compiled,
+        // the COPY = false form issues the first tap reads right behind this store with no vmcnt
+        // wait between (tests/test_resident_loop_waits_cpu.py); the COPY = true form waits here
+        // for its copy's load, and with it for this store
         if (active && t + 2 < a.T) {
             if (ex) PixVec<T, PX>::template poison<kSc1>(make_rsrc(p_out + a.tstride), vpix);
             else PixVec<T, PX>::template poison<0>(make_rsrc(p_out + a.tstride), vpix);
@@ -1411,7 +1439,9 @@ __global__ void __launch_bounds__(MAXNT) prop_resident_kernel(ResArgs a) {
                 o[e] = vv;
                 fin[e] = clip ? vv : clamp0(vv);  // :375-377
             }
-            // plane t + 1's poison acknowledged first (issued before the taps: no wait left)
+            // plane t + 1's poison acknowledged first: the hand-off's one ordering rule, and in the
+            // COPY = false form the loop's only vmcnt wait outside the staging (the poison was
+            // issued before the taps, so they cover its acknowledgement)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (ex) PixVec<T, PX>::template store<kSc1>(make_rsrc(p_out), vpix, 0u, o);  // write-through
             else PixVec<T, PX>::template store<0>(make_rsrc(p_out), vpix, 0u, o);   // kept in the XCD's L2
@@ -1516,10 +1546,23 @@ __global__ void __launch_bounds__(MAXNT) prop_resident_kernel(ResArgs a) {
 #define NLSPN_RES_BUILDS_WIDE(X)                                                                    \
     X(1, 17, 0, false, false, 0) X(1, 17, 576, false, false, 0) X(1, 17, 576, true, false, 0)       \
     X(1, 17, 0, true, false, 0) X(5, 5, 0, false, false, 0)
+// The builds that copy in the loop, once more without the copy code (COPY = false: the helper
+// launches of C2, C3 and C5, and calls without the offsets output), as X(KH, KW, NTC, GROUPS, FIRST).
+#define NLSPN_RES_NOCOPY_3X3(X)                                                                     \
+    X(3, 3, 0, false, true) X(3, 3, 576, false, true) X(3, 3, 576, true, true) X(3, 3, 0, false, false) \
+    X(3, 3, 576, false, false) X(3, 3, 576, true, false) X(3, 3, 0, true, false)
+#define NLSPN_RES_NOCOPY_WIDE(X)                                                                    \
+    X(1, 17, 0, false, false) X(1, 17, 576, false, false) X(1, 17, 576, true, false)                \
+    X(1, 17, 0, true, false) X(5, 5, 0, false, false)
 #define NLSPN_RES_SPEC(LINKAGE, KH, KW, NTC, G, F, PXO)                                                                  \
     LINKAGE template __global__ void prop_resident_kernel<float, KH, KW, kResMaxNT, kResSMax, NTC, G, F, PXO>(ResArgs);  \
     LINKAGE template __global__ void prop_resident_kernel<__half, KH, KW, kResMaxNT, kResSMax, NTC, G, F, PXO>(ResArgs);
+#define NLSPN_RES_SPEC_NOCOPY(LINKAGE, KH, KW, NTC, G, F)                                                                      \
+    LINKAGE template __global__ void prop_resident_kernel<float, KH, KW, kResMaxNT, kResSMax, NTC, G, F, 0, false>(ResArgs);  \
+    LINKAGE template __global__ void prop_resident_kernel<__half, KH, KW, kResMaxNT, kResSMax, NTC, G, F, 0, false>(ResArgs);
 #define NLSPN_RES_INST(...) NLSPN_RES_SPEC(, __VA_ARGS__)
+#define NLSPN_RES_INST_NOCOPY(...) NLSPN_RES_SPEC_NOCOPY(, __VA_ARGS__)
+#define NLSPN_RES_EXTERN_NOCOPY(...) NLSPN_RES_SPEC_NOCOPY(extern, __VA_ARGS__)
 #define NLSPN_RES_EXTERN(...) NLSPN_RES_SPEC(extern, __VA_ARGS__)
 
 }  // namespace nlspn
