@@ -32,10 +32,10 @@
 #pragma once
 
 #include "nlspn_gconv.h"
+#include "nlspn_gwgrad_plan.h"  // kGwBW (pixels per unit at most) and the plan of a call
 
 namespace nlspn {
 
-constexpr int kGwBW = 64;     // pixels per unit at most (a multiple of 4)
 constexpr int kGwGP = 66;     // small row pitch per channel (>= kGwBW, = 2 mod 32)
 constexpr int kGwHALF = 80;   // stride 2: offset of the odd columns in a window row (>= kGwBW + 1, = 16 mod 32)
 // window row pitch: 3 pitches = 2 (mod 32), i.e. the pitch = 22 (mod 32)
@@ -171,7 +171,8 @@ __global__ void ggates_kernel(GgatesArgs a, int stage);
 
 // The weight-gradient tilings: X(S, WM, WGM, WGN).  64 x 32 channels for the wide layers; 128 x 16
 // when the large tensor has at most 16 channels; one wave (16 x 16) for the narrow layers (1 / 9
-// -> 16, 16 -> 8), which are bound by their few MB of traffic.
+// -> 16, 16 -> 8), which are bound by their few MB of traffic.  (Which one a shape takes:
+// gw_choose, nlspn_gwgrad_plan.h.)
 #define NLSPN_GW_CONFIGS(X) \
     X(1, 2, 2, 2)           \
     X(2, 2, 2, 2)           \

@@ -28,15 +28,23 @@ NLSPN_GW16_CONFIGS(NLSPN_GW16_EXTERN)
 using namespace nlspn;
 
 namespace {
+// A preset of either family.  cc: the input channels of a chunk as packed (f32: kGcCP, which
+// every chunk size divides; f16: the chunk's CCB blocks of 8).
 struct GcPreset {
     const void *fn;
-    int mode, wgco, npx, xr, xp, lds, epi;
+    int mode, wgco, npx, xr, xp, cc, lds, epi;
 };
 template <int MODE, int WM, int WN, int WGM, int WGN, int XR, int XP, int CC, int EPI>
 GcPreset gc_preset() {
     using Cfg = GcCfg<MODE, WM, WN, WGM, WGN, XR, XP, CC, EPI>;
     return GcPreset{reinterpret_cast<const void *>(&gconv_kernel<MODE, WM, WN, WGM, WGN, XR, XP, CC, EPI>), MODE,
-                    Cfg::WGCO, Cfg::NPX, XR, XP, (int)(Cfg::LDS_FLOATS * sizeof(float)), EPI};
+                    Cfg::WGCO, Cfg::NPX, XR, XP, kGcCP, (int)(Cfg::LDS_FLOATS * sizeof(float)), EPI};
+}
+template <int MODE, int WM, int WN, int WGM, int WGN, int XR, int XP, int CCB, int EPI>
+GcPreset gc16_preset() {
+    using Cfg = Gc16Cfg<MODE, WM, WN, WGM, WGN, XR, XP, CCB, EPI>;
+    return GcPreset{reinterpret_cast<const void *>(&gconv16_kernel<MODE, WM, WN, WGM, WGN, XR, XP, CCB, EPI>), MODE,
+                    Cfg::WGCO, Cfg::NPX, XR, XP, 8 * CCB, Cfg::LDS_BYTES, EPI};
 }
 bool gc_get(int layer, GcPreset &p) {
     switch (layer) {
@@ -47,38 +55,67 @@ bool gc_get(int layer, GcPreset &p) {
         default: return false;
     }
 }
-}  // namespace
-extern "C" {
-
-int nlspn_gconv_pack_layout(int layer, int *co_tile, int *cin_chunk, int *transposed) {
-    if (layer == NLSPN_GC_S2_SMALL) {  // the module's own weight layout
-        if (co_tile) *co_tile = 0;
-        if (cin_chunk) *cin_chunk = 1;
-        if (transposed) *transposed = 0;
-        return NLSPN_OK;
+bool gc16_get(int layer, GcPreset &p) {
+    switch (layer) {
+#define NLSPN_GC16_CASE(id, ...) \
+    case id: p = gc16_preset<__VA_ARGS__>(); return true;
+        NLSPN_GC16_CONFIGS(NLSPN_GC16_CASE)
+        default: return false;
     }
-    GcPreset p;
-    if (!gc_get(layer, p)) return fail(NLSPN_EINVAL, "unknown GRU-mode conv preset %d", layer);
-    if (co_tile) *co_tile = p.wgco;
-    if (cin_chunk) *cin_chunk = kGcCP;
-    if (transposed) *transposed = p.mode == kGcT2;
-    return NLSPN_OK;
 }
 
-}  // extern "C"
-namespace {
+// ---- the steps the f32 forward, the data gradient and the f16 forward share
+// the packing of a preset's weights (p null: the VALU kernel reads the module's own layout)
+int gc_pack_layout(const GcPreset *p, int *co_tile, int *cin_chunk, int *transposed) {
+    if (co_tile) *co_tile = p ? p->wgco : 0;
+    if (cin_chunk) *cin_chunk = p ? p->cc : 1;
+    if (transposed) *transposed = p && p->mode == kGcT2;
+    return NLSPN_OK;
+}
+// the output size of a mode, before any crop
+void gc_out_size(int mode, int Hi, int Wi, int &Ho, int &Wo) {
+    if (mode == kGcS1) { Ho = Hi; Wo = Wi; }
+    else if (mode == kGcS2) { Ho = (Hi - 1) / 2 + 1; Wo = (Wi - 1) / 2 + 1; }
+    else { Ho = 2 * Hi; Wo = 2 * Wi; }
+}
 // the pixel tiling of a launch (a.Hi / a.Wi / a.Ho / a.Wo set): column bands and tiles per band
-// (gc_tile, nlspn_gconv_plan.h)
-int gc_tile(const GcPreset &p, GconvArgs &a) {
+// (gc_tile, nlspn_gconv_plan.h); who: the family in the error text
+template <class Args>
+int gc_tile(const GcPreset &p, Args &a, const char *who) {
     GcTiling t;
     const bool ok = nlspn::gc_tile(GcGeo{p.mode, p.wgco, p.npx, p.xr, p.xp}, p.mode == kGcT2 ? a.Hi : a.Ho,
                                    p.mode == kGcT2 ? a.Wi : a.Wo, t);
     a.gh = t.gh; a.gw = t.gw; a.bw = t.bw; a.nbands = t.nbands; a.tpb = t.tpb; a.npx = t.npx;
     if (!ok)
-        return fail(NLSPN_EUNSUPPORTED, "gconv: a tile of a %d-wide band spans more than %d window rows", a.bw, p.xr);
+        return fail(NLSPN_EUNSUPPORTED, "%s: a tile of a %d-wide band spans more than %d window rows", who, a.bw, p.xr);
     return NLSPN_OK;
 }
+// the workgroups of a tiled launch (a.co_tiles set; GRU1: the qx workgroups take two pixel tiles each)
+template <class Args>
+long long gc_wgs(const GcPreset &p, const Args &a) {
+    if (p.epi == kGcEpiGru1) return gc_gru1_wgs(a.hc, p.wgco, a.co_tiles, gc_rest_count(a.B, a.nbands, a.tpb));
+    return (long long)(p.mode == kGcT2 ? 4 : 1) * a.co_tiles * a.B * a.nbands * a.tpb;
+}
+// the VALU kernels' grid: a thread per stored pixel, grid-stride past 2^20 workgroups
+unsigned gs_grid(long long npix) { return (unsigned)std::min<long long>((npix + kGsNT - 1) / kGsNT, 1 << 20); }
+template <class Args>
+int gc_launch(const GcPreset &p, Args &a, long long nwg, void *stream, const char *what) {
+    NLSPN_TRY(set_lds_attr(p.fn, p.lds));
+    void *args[] = {&a};
+    return launch_kernel(p.fn, dim3((unsigned)nwg), dim3(kGcNT), args, (size_t)p.lds, as_stream(stream), what);
+}
+}  // namespace
+extern "C" {
 
+int nlspn_gconv_pack_layout(int layer, int *co_tile, int *cin_chunk, int *transposed) {
+    GcPreset p;
+    const bool small = layer == NLSPN_GC_S2_SMALL;
+    if (!small && !gc_get(layer, p)) return fail(NLSPN_EINVAL, "unknown GRU-mode conv preset %d", layer);
+    return gc_pack_layout(small ? nullptr : &p, co_tile, cin_chunk, transposed);
+}
+
+}  // extern "C"
+namespace {
 // nlspn_gconv, and with gamma / aff_kind nlspn_gconv_affnorm (preset NLSPN_GC_T2_AFF)
 int gconv_impl(int layer, const float *x0, int c0, const float *x1, int c1, const float *wpk, const float *bias,
                float *y, const float *h, float *zb, float *rhb, float *qxb, float *hout, int B, int Hi, int Wi,
@@ -92,16 +129,13 @@ int gconv_impl(int layer, const float *x0, int c0, const float *x1, int c1, cons
         if (!x0 || !wpk || !bias || !y) return fail(NLSPN_EINVAL, "gconv small: null pointer");
         GconvArgs a{};
         a.x0 = x0; a.bias = bias; a.y = y; a.c0 = c0; a.B = B; a.Hi = Hi; a.Wi = Wi;
-        a.Ho = (Hi - 1) / 2 + 1;
-        a.Wo = (Wi - 1) / 2 + 1;
+        gc_out_size(kGcS2, Hi, Wi, a.Ho, a.Wo);
         a.ohs = ohs; a.ows = ows; a.cout = cout; a.act = act; a.in_div = in_div;
         if (ohs < 1 || ows < 1 || ohs > a.Ho || ows > a.Wo)
             return fail(NLSPN_EINVAL, "gconv small: stored size %dx%d outside the output %dx%d", ohs, ows, a.Ho, a.Wo);
-        const long long npix = (long long)B * ohs * ows;
-        const unsigned grid = (unsigned)std::min<long long>((npix + kGsNT - 1) / kGsNT, 1 << 20);
         void *args[] = {&a, const_cast<float **>(&wpk)};
-        return launch_kernel(reinterpret_cast<const void *>(&gsmall_kernel<16>), dim3(grid), dim3(kGsNT), args, 0,
-                             as_stream(stream), "nlspn_gconv small");
+        return launch_kernel(reinterpret_cast<const void *>(&gsmall_kernel<16>), dim3(gs_grid((long long)B * ohs * ows)),
+                             dim3(kGsNT), args, 0, as_stream(stream), "nlspn_gconv small");
     }
     GcPreset p;
     if (!gc_get(layer, p)) return fail(NLSPN_EINVAL, "unknown GRU-mode conv preset %d", layer);
@@ -129,9 +163,7 @@ int gconv_impl(int layer, const float *x0, int c0, const float *x1, int c1, cons
     a.rb = rb; a.qb = qb;
     a.c0 = c0; a.c1 = c1; a.cin_pad = (c0 + c1 + kGcCP - 1) / kGcCP * kGcCP;
     a.B = B; a.Hi = Hi; a.Wi = Wi;
-    if (p.mode == kGcS1) { a.Ho = Hi; a.Wo = Wi; }
-    else if (p.mode == kGcS2) { a.Ho = (Hi - 1) / 2 + 1; a.Wo = (Wi - 1) / 2 + 1; }
-    else { a.Ho = 2 * Hi; a.Wo = 2 * Wi; }
+    gc_out_size(p.mode, Hi, Wi, a.Ho, a.Wo);
     a.ohs = gru ? a.Ho : ohs;
     a.ows = gru ? a.Wo : ows;
     if (a.ohs < 1 || a.ows < 1 || a.ohs > a.Ho || a.ows > a.Wo)
@@ -151,9 +183,8 @@ int gconv_impl(int layer, const float *x0, int c0, const float *x1, int c1, cons
     } else if (!y) {
         return fail(NLSPN_EINVAL, "gconv: null output");
     }
-    NLSPN_TRY(gc_tile(p, a));
-    long long nwg = (long long)(p.mode == kGcT2 ? 4 : 1) * a.co_tiles * B * a.nbands * a.tpb;
-    if (gru1) nwg = gc_gru1_wgs(a.hc, p.wgco, a.co_tiles, gc_rest_count(a.B, a.nbands, a.tpb));  // (the qx workgroups take two pixel tiles each)
+    NLSPN_TRY(gc_tile(p, a, "gconv"));
+    const long long nwg = gc_wgs(p, a);
     // Small grids: the same layer kind on 32-pixel tiles (the same co tile, hence the same packed
     // weights) when 64-pixel tiles would leave most CUs one workgroup (NYU B=8: the 1/8-scale last
     // encoder conv 104.1 -> 85.2 us, GRU2 52.6 -> 50.6 us; profiles/r06/gc_bench_layers_v4_n32.json)
@@ -163,9 +194,7 @@ int gconv_impl(int layer, const float *x0, int c0, const float *x1, int c1, cons
     // (one image's channels of a source within a 32-bit buffer descriptor)
     if (nwg > 0x7fffffffLL || (long long)std::max(c0, c1) * Hi * Wi * 4 > 0x7fffffffLL)
         return fail(NLSPN_EINVAL, "gconv: problem too large");
-    NLSPN_TRY(set_lds_attr(p.fn, p.lds));
-    void *args[] = {&a};
-    return launch_kernel(p.fn, dim3((unsigned)nwg), dim3(kGcNT), args, (size_t)p.lds, as_stream(stream), "nlspn_gconv");
+    return gc_launch(p, a, nwg, stream, "nlspn_gconv");
 }
 }  // namespace
 extern "C" {
@@ -188,115 +217,19 @@ int nlspn_gconv_affnorm(const float *x0, int c0, const float *wpk, const float *
 // ---------------------------------------------------------------- backward (nlspn_gconv_bwd.h)
 }  // extern "C"
 namespace {
-struct GwPreset {
-    const void *fn;
-    int mt, nt, nthr, lds;
-};
+// The kernel of a tiling (nullptr: none instantiated); the f32 kernels' LDS bytes come with it
 template <int S, int WM, int WGM, int WGN>
-GwPreset gw_preset() {
-    using Cfg = GwCfg<S, WM, WGM, WGN>;
-    return GwPreset{reinterpret_cast<const void *>(&gwgrad_kernel<S, WM, WGM, WGN>), Cfg::MT, Cfg::NT, Cfg::NTHR,
-                    (int)(Cfg::LDS_FLOATS * sizeof(float))};
+const void *gw_fn(const GwGeo &g, int &lds) {
+    if (g.S != S || g.wm != WM || g.wgm != WGM || g.wgn != WGN) return nullptr;
+    lds = (int)(GwCfg<S, WM, WGM, WGN>::LDS_FLOATS * sizeof(float));
+    return reinterpret_cast<const void *>(&gwgrad_kernel<S, WM, WGM, WGN>);
 }
-// The plan of one weight-gradient call, a pure function of the shape: the tiling by channel
-// counts, the K slices so that about kGwTargetWgs workgroups run (a constant, not the device's
-// CU count: the summation order, hence the bits, is the same on every device).
-constexpr int kGwTargetWgs = 512, kGwMaxBiasSlices = 64;
-struct GwPlan {
-    GwPreset p;
-    int mtiles, ntiles, nsl, bw, nbands, units, ups, nsb;
-    long long slab, bias_off, floats;  // slab floats; the bias partials' offset; the workspace's floats
-};
-int gw_plan(int stride, int Cs, int Cl, int B, int Hs, int Ws, int Hl, int Wl, GwPlan &pl) {
-    if (stride != 1 && stride != 2) return fail(NLSPN_EINVAL, "gconv wgrad: stride %d (supported 1, 2)", stride);
-    if (B < 1 || Cs < 1 || Cl < 1 || Hs < 1 || Ws < 1 || Hl < 1 || Wl < 1)
-        return fail(NLSPN_EINVAL, "gconv wgrad: bad shape B=%d Cs=%d Cl=%d small %dx%d large %dx%d", B, Cs, Cl, Hs, Ws, Hl, Wl);
-    if (stride == 1 ? (Hl != Hs || Wl != Ws) : (Hl > 2 * Hs || Wl > 2 * Ws))
-        return fail(NLSPN_EINVAL, "gconv wgrad: large size %dx%d does not belong to small size %dx%d at stride %d", Hl, Wl,
-                    Hs, Ws, stride);
-    if ((long long)B * Hs > 0x3fffffffLL / ((Ws + kGwBW - 1) / kGwBW)) return fail(NLSPN_EINVAL, "gconv wgrad: problem too large");
-    pl.p = stride == 1 ? gw_preset<1, 2, 2, 2>()
-           : Cl > 16   ? gw_preset<2, 2, 2, 2>()
-           : Cs > 16   ? gw_preset<2, 2, 4, 1>()
-                       : gw_preset<2, 1, 1, 1>();
-    pl.mtiles = (Cs + pl.p.mt - 1) / pl.p.mt;
-    pl.ntiles = (Cl + pl.p.nt - 1) / pl.p.nt;
-    pl.nbands = (Ws + kGwBW - 1) / kGwBW;
-    pl.bw = (Ws + pl.nbands - 1) / pl.nbands;
-    pl.units = B * Hs * pl.nbands;
-    const int tiles = pl.mtiles * pl.ntiles;
-    int nsl = std::max(1, std::min(pl.units, (kGwTargetWgs + tiles - 1) / tiles));
-    pl.ups = (pl.units + nsl - 1) / nsl;
-    pl.nsl = (pl.units + pl.ups - 1) / pl.ups;
-    pl.slab = (long long)pl.mtiles * pl.p.mt * pl.ntiles * pl.p.nt * 9;
-    pl.nsb = (int)std::max(1LL, std::min<long long>(kGwMaxBiasSlices, ((long long)B * Hl * Wl + 16383) / 16384));
-    pl.bias_off = pl.slab * pl.nsl;
-    pl.floats = pl.bias_off + (long long)pl.nsb * std::max(Cs, Cl);
-    return NLSPN_OK;
+const void *gw_kernel_of(const GwGeo &g, int &lds) {
+    const void *fn = nullptr;
+#define NLSPN_GW_PICK(...) if (!fn) fn = gw_fn<__VA_ARGS__>(g, lds);
+    NLSPN_GW_CONFIGS(NLSPN_GW_PICK)
+    return fn;
 }
-}  // namespace
-extern "C" {
-
-size_t nlspn_gconv_wgrad_workspace_bytes(int stride, int Cs, int Cl, int B, int Hs, int Ws, int Hl, int Wl) {
-    GwPlan pl;
-    return gw_plan(stride, Cs, Cl, B, Hs, Ws, Hl, Wl, pl) ? 0 : (size_t)pl.floats * sizeof(float);
-}
-
-int nlspn_gconv_wgrad(int stride, const float *s, int Cs, const float *l0, int c0, const float *l1, int c1, float *dw,
-                      float *db, int bias_from_large, float scale, void *workspace, int64_t workspace_bytes, int B,
-                      int Hs, int Ws, int Hl, int Wl, void *stream) {
-    if (!s || !l0 || !dw || !workspace) return fail(NLSPN_EINVAL, "gconv wgrad: null tensor, gradient or workspace");
-    if (c0 < 1 || c1 < 0 || (c1 > 0 && !l1)) return fail(NLSPN_EINVAL, "gconv wgrad: bad channels c0=%d c1=%d", c0, c1);
-    // (a 16-channel block of the large tensor reads one source)
-    if (c1 > 0 && c0 % 16 != 0)
-        return fail(NLSPN_EINVAL, "gconv wgrad: a channel block would straddle the two sources (c0 = %d, not a multiple of 16)", c0);
-    if (db && bias_from_large && c1 > 0) return fail(NLSPN_EINVAL, "gconv wgrad: the bias gradient reads one source");
-    GwPlan pl;
-    NLSPN_TRY(gw_plan(stride, Cs, c0 + c1, B, Hs, Ws, Hl, Wl, pl));
-    if (workspace_bytes < pl.floats * (long long)sizeof(float))
-        return fail(NLSPN_EINVAL, "gconv wgrad: workspace too small (%lld bytes, needs %lld)", (long long)workspace_bytes,
-                    pl.floats * (long long)sizeof(float));
-    GwgradArgs a{};
-    a.s = s; a.l0 = l0; a.l1 = l1; a.ws = static_cast<float *>(workspace);
-    a.Cs = Cs; a.c0 = c0; a.c1 = c1; a.B = B; a.Hs = Hs; a.Ws = Ws; a.Hl = Hl; a.Wl = Wl;
-    a.mtiles = pl.mtiles; a.ntiles = pl.ntiles; a.nsl = pl.nsl;
-    a.bw = pl.bw; a.nbands = pl.nbands; a.units = pl.units; a.ups = pl.ups;
-    const int Cl = c0 + c1;
-    hipStream_t st = as_stream(stream);
-    NLSPN_TRY(set_lds_attr(pl.p.fn, pl.p.lds));
-    void *args[] = {&a};
-    NLSPN_TRY(launch_kernel(pl.p.fn, dim3((unsigned)(pl.mtiles * pl.ntiles * pl.nsl)), dim3(pl.p.nthr), args,
-                            (size_t)pl.p.lds, st, "nlspn_gconv_wgrad"));
-    {
-        const float *wsp = a.ws;
-        int n0 = Cs, n1 = Cl, n1p = pl.ntiles * pl.p.nt, T = 9, nsl = pl.nsl;
-        long long slab = pl.slab;
-        void *rargs[] = {&wsp, &dw, &n0, &n1, &n1p, &T, &slab, &nsl, &scale};
-        NLSPN_TRY(launch_kernel(reinterpret_cast<const void *>(&gwgrad_reduce_kernel),
-                                dim3(elementwise_grid((long long)Cs * Cl * 9)), dim3(256), rargs, 0, st,
-                                "nlspn_gconv_wgrad reduce"));
-    }
-    if (db) {
-        const float *g = bias_from_large ? l0 : s;
-        int C = bias_from_large ? Cl : Cs, nsb = pl.nsb, one = 1;
-        long long HW = bias_from_large ? (long long)Hl * Wl : (long long)Hs * Ws;
-        float *part = a.ws + pl.bias_off;
-        void *pargs[] = {&g, &part, &C, &B, &HW, &nsb};
-        NLSPN_TRY(launch_kernel(reinterpret_cast<const void *>(&gbias_partial_kernel), dim3((unsigned)(C * nsb)), dim3(256),
-                                pargs, 0, st, "nlspn_gconv_wgrad bias"));
-        const float *cpart = part;
-        long long bslab = C;
-        float unit = 1.f;
-        void *rargs[] = {&cpart, &db, &C, &one, &one, &one, &bslab, &nsb, &unit};
-        NLSPN_TRY(launch_kernel(reinterpret_cast<const void *>(&gwgrad_reduce_kernel), dim3(elementwise_grid(C)), dim3(256),
-                                rargs, 0, st, "nlspn_gconv_wgrad bias reduce"));
-    }
-    return NLSPN_OK;
-}
-
-// ---- the split-bf16 weight gradient (nlspn_gwgrad16.h): the same call on the bf16 matrix cores
-}  // extern "C"
-namespace {
 template <int S, int WM, int WGM, int WGN>
 const void *gw16_fn(const Gw16Geo &g) {
     return g.S == S && g.wm == WM && g.wgm == WGM && g.wgn == WGN
@@ -308,75 +241,140 @@ const void *gw16_kernel_of(const Gw16Geo &g) {
     NLSPN_GW16_CONFIGS(NLSPN_GW16_PICK)
     return fn;
 }
-}  // namespace
-extern "C" {
 
-size_t nlspn_gconv_wgrad_bf16x3_workspace_bytes(int stride, int Cs, int Cl, int B, int Hs, int Ws, int Hl, int Wl) {
-    GwPlan f32;
-    if (gw_plan(stride, Cs, Cl, B, Hs, Ws, Hl, Wl, f32)) return 0;  // (the shape rules are the f32 entry's)
-    if (gw16_choose(stride, Cs, Cl) == kGw16F32) return (size_t)f32.floats * sizeof(float);
-    return (size_t)gw16_plan(stride, Cs, Cl, B, Hs, Ws, Hl, Wl).floats * sizeof(float);
+// The shape rules of a weight-gradient call, for both entries and both workspace queries (the
+// plans themselves are pure arithmetic on a shape that passed: nlspn_gwgrad_plan.h,
+// nlspn_gwgrad16_plan.h; kGw16BW = kGwBW, so one unit-count bound serves both)
+static_assert(kGw16BW == kGwBW, "one unit-count bound for both plans");
+int gw_check_shape(int stride, int Cs, int Cl, int B, int Hs, int Ws, int Hl, int Wl) {
+    if (stride != 1 && stride != 2) return fail(NLSPN_EINVAL, "gconv wgrad: stride %d (supported 1, 2)", stride);
+    if (B < 1 || Cs < 1 || Cl < 1 || Hs < 1 || Ws < 1 || Hl < 1 || Wl < 1)
+        return fail(NLSPN_EINVAL, "gconv wgrad: bad shape B=%d Cs=%d Cl=%d small %dx%d large %dx%d", B, Cs, Cl, Hs, Ws, Hl, Wl);
+    if (stride == 1 ? (Hl != Hs || Wl != Ws) : (Hl > 2 * Hs || Wl > 2 * Ws))
+        return fail(NLSPN_EINVAL, "gconv wgrad: large size %dx%d does not belong to small size %dx%d at stride %d", Hl, Wl,
+                    Hs, Ws, stride);
+    if ((long long)B * Hs > 0x3fffffffLL / ((Ws + kGwBW - 1) / kGwBW)) return fail(NLSPN_EINVAL, "gconv wgrad: problem too large");
+    return NLSPN_OK;
 }
-
-int nlspn_gconv_wgrad_bf16x3(int stride, const float *s, int Cs, const float *l0, int c0, const float *l1, int c1,
-                             float *dw, float *db, int bias_from_large, float scale, void *workspace,
-                             int64_t workspace_bytes, int B, int Hs, int Ws, int Hl, int Wl, void *stream) {
+// ... preceded, in an entry, by the rules of its tensors
+int gw_check_call(int stride, const float *s, int Cs, const float *l0, int c0, const float *l1, int c1, const float *dw,
+                  const float *db, int bias_from_large, const void *workspace, int B, int Hs, int Ws, int Hl, int Wl) {
     if (!s || !l0 || !dw || !workspace) return fail(NLSPN_EINVAL, "gconv wgrad: null tensor, gradient or workspace");
     if (c0 < 1 || c1 < 0 || (c1 > 0 && !l1)) return fail(NLSPN_EINVAL, "gconv wgrad: bad channels c0=%d c1=%d", c0, c1);
+    // (a 16-channel block of the large tensor reads one source)
     if (c1 > 0 && c0 % 16 != 0)
         return fail(NLSPN_EINVAL, "gconv wgrad: a channel block would straddle the two sources (c0 = %d, not a multiple of 16)", c0);
     if (db && bias_from_large && c1 > 0) return fail(NLSPN_EINVAL, "gconv wgrad: the bias gradient reads one source");
-    const int Cl = c0 + c1;
-    GwPlan f32;
-    NLSPN_TRY(gw_plan(stride, Cs, Cl, B, Hs, Ws, Hl, Wl, f32));
-    // both channel counts <= 16: the one-wave f32 kernel, bit for bit (its cost is staging, not MFMA)
-    if (gw16_choose(stride, Cs, Cl) == kGw16F32)
-        return nlspn_gconv_wgrad(stride, s, Cs, l0, c0, l1, c1, dw, db, bias_from_large, scale, workspace, workspace_bytes,
-                                 B, Hs, Ws, Hl, Wl, stream);
-    const Gw16Plan pl = gw16_plan(stride, Cs, Cl, B, Hs, Ws, Hl, Wl);
-    if (workspace_bytes < pl.floats * (long long)sizeof(float))
+    return gw_check_shape(stride, Cs, c0 + c1, B, Hs, Ws, Hl, Wl);
+}
+int gw_check_workspace(int64_t workspace_bytes, long long floats) {
+    if (workspace_bytes < floats * (long long)sizeof(float))
         return fail(NLSPN_EINVAL, "gconv wgrad: workspace too small (%lld bytes, needs %lld)", (long long)workspace_bytes,
-                    pl.floats * (long long)sizeof(float));
-    // (the kernel's per-thread staging offsets are 32 bits: a pass's 8 channel planes and one window row)
-    if ((long long)pl.mtiles * pl.ntiles * pl.nsl > 0x7fffffffLL || (long long)Hs * Ws > (1LL << 27) || (long long)Hl * Wl > (1LL << 27))
-        return fail(NLSPN_EINVAL, "gconv wgrad: problem too large");
-    const void *fn = gw16_kernel_of(pl.g);
-    if (!fn) return fail(NLSPN_EUNSUPPORTED, "gconv wgrad bf16x3: no kernel for tiling %d", pl.tiling);
+                    floats * (long long)sizeof(float));
+    return NLSPN_OK;
+}
+
+// the kernels' arguments of a planned call
+GwgradArgs gw_args(const float *s, int Cs, const float *l0, int c0, const float *l1, int c1, void *workspace, int B,
+                   int Hs, int Ws, int Hl, int Wl, const GwSplit &pl) {
     GwgradArgs a{};
     a.s = s; a.l0 = l0; a.l1 = l1; a.ws = static_cast<float *>(workspace);
     a.Cs = Cs; a.c0 = c0; a.c1 = c1; a.B = B; a.Hs = Hs; a.Ws = Ws; a.Hl = Hl; a.Wl = Wl;
     a.mtiles = pl.mtiles; a.ntiles = pl.ntiles; a.nsl = pl.nsl;
     a.bw = pl.bw; a.nbands = pl.nbands; a.units = pl.units; a.ups = pl.ups;
+    return a;
+}
+// The launches of a planned call: the slabs by the tiling's kernel fn (nthr threads, lds bytes,
+// nt large channels per tile), their sum into dw in slice order, and the bias gradient's
+// partials and their sum.  All but the first are the same kernels on the same slices for every
+// precision (pl.nsb is gw_split's, a function of B Hl Wl alone): the bias gradient is bit-equal
+// between the entries.  what: the labels of the four launches, naming the entry that was called.
+struct GwLabels {
+    const char *slabs, *reduce, *bias, *bias_reduce;
+};
+#define NLSPN_GW_LABELS(entry) GwLabels{entry, entry " reduce", entry " bias", entry " bias reduce"}
+int gw_launch(const void *fn, int nthr, int lds, int nt, GwgradArgs &a, const GwSplit &pl, float *dw, float *db,
+              int bias_from_large, float scale, void *stream, const GwLabels &what) {
+    const int Cs = a.Cs, Cl = a.c0 + a.c1;
     hipStream_t st = as_stream(stream);
-    NLSPN_TRY(set_lds_attr(fn, pl.g.lds_bytes()));
+    NLSPN_TRY(set_lds_attr(fn, lds));
     void *args[] = {&a};
-    NLSPN_TRY(launch_kernel(fn, dim3((unsigned)(pl.mtiles * pl.ntiles * pl.nsl)), dim3(pl.g.nthr()), args,
-                            (size_t)pl.g.lds_bytes(), st, "nlspn_gconv_wgrad_bf16x3"));
-    {   // the slab reduce: the f32 entry's kernel and order
+    NLSPN_TRY(launch_kernel(fn, dim3((unsigned)(pl.mtiles * pl.ntiles * pl.nsl)), dim3(nthr), args, (size_t)lds, st,
+                            what.slabs));
+    {
         const float *wsp = a.ws;
-        int n0 = Cs, n1 = Cl, n1p = pl.ntiles * pl.g.nt(), T = 9, nsl = pl.nsl;
+        int n0 = Cs, n1 = Cl, n1p = pl.ntiles * nt, T = 9, nsl = pl.nsl;
         long long slab = pl.slab;
         void *rargs[] = {&wsp, &dw, &n0, &n1, &n1p, &T, &slab, &nsl, &scale};
         NLSPN_TRY(launch_kernel(reinterpret_cast<const void *>(&gwgrad_reduce_kernel),
-                                dim3(elementwise_grid((long long)Cs * Cl * 9)), dim3(256), rargs, 0, st,
-                                "nlspn_gconv_wgrad_bf16x3 reduce"));
+                                dim3(elementwise_grid((long long)Cs * Cl * 9)), dim3(256), rargs, 0, st, what.reduce));
     }
-    if (db) {  // the bias gradient: the f32 entry's launches with its slice count (bit-equal)
-        const float *g = bias_from_large ? l0 : s;
-        int C = bias_from_large ? Cl : Cs, nsb = f32.nsb, one = 1;
-        long long HW = bias_from_large ? (long long)Hl * Wl : (long long)Hs * Ws;
+    if (db) {
+        const float *g = bias_from_large ? a.l0 : a.s;
+        int C = bias_from_large ? Cl : Cs, B = a.B, nsb = pl.nsb, one = 1;
+        long long HW = bias_from_large ? (long long)a.Hl * a.Wl : (long long)a.Hs * a.Ws;
         float *part = a.ws + pl.bias_off;
         void *pargs[] = {&g, &part, &C, &B, &HW, &nsb};
         NLSPN_TRY(launch_kernel(reinterpret_cast<const void *>(&gbias_partial_kernel), dim3((unsigned)(C * nsb)), dim3(256),
-                                pargs, 0, st, "nlspn_gconv_wgrad_bf16x3 bias"));
+                                pargs, 0, st, what.bias));
         const float *cpart = part;
         long long bslab = C;
         float unit = 1.f;
         void *rargs[] = {&cpart, &db, &C, &one, &one, &one, &bslab, &nsb, &unit};
         NLSPN_TRY(launch_kernel(reinterpret_cast<const void *>(&gwgrad_reduce_kernel), dim3(elementwise_grid(C)), dim3(256),
-                                rargs, 0, st, "nlspn_gconv_wgrad_bf16x3 bias reduce"));
+                                rargs, 0, st, what.bias_reduce));
     }
     return NLSPN_OK;
+}
+}  // namespace
+extern "C" {
+
+size_t nlspn_gconv_wgrad_workspace_bytes(int stride, int Cs, int Cl, int B, int Hs, int Ws, int Hl, int Wl) {
+    if (gw_check_shape(stride, Cs, Cl, B, Hs, Ws, Hl, Wl)) return 0;
+    return (size_t)gw_plan(stride, Cs, Cl, B, Hs, Ws, Hl, Wl).floats * sizeof(float);
+}
+
+int nlspn_gconv_wgrad(int stride, const float *s, int Cs, const float *l0, int c0, const float *l1, int c1, float *dw,
+                      float *db, int bias_from_large, float scale, void *workspace, int64_t workspace_bytes, int B,
+                      int Hs, int Ws, int Hl, int Wl, void *stream) {
+    NLSPN_TRY(gw_check_call(stride, s, Cs, l0, c0, l1, c1, dw, db, bias_from_large, workspace, B, Hs, Ws, Hl, Wl));
+    const GwPlan pl = gw_plan(stride, Cs, c0 + c1, B, Hs, Ws, Hl, Wl);
+    NLSPN_TRY(gw_check_workspace(workspace_bytes, pl.floats));
+    int lds = 0;
+    const void *fn = gw_kernel_of(pl.g, lds);
+    if (!fn) return fail(NLSPN_EUNSUPPORTED, "gconv wgrad: no kernel for the tiling of stride %d, Cs %d, Cl %d", stride, Cs, c0 + c1);
+    GwgradArgs a = gw_args(s, Cs, l0, c0, l1, c1, workspace, B, Hs, Ws, Hl, Wl, pl);
+    return gw_launch(fn, pl.g.nthr(), lds, pl.g.nt(), a, pl, dw, db, bias_from_large, scale, stream,
+                     NLSPN_GW_LABELS("nlspn_gconv_wgrad"));
+}
+
+// ---- the split-bf16 weight gradient (nlspn_gwgrad16.h): the same call on the bf16 matrix cores
+size_t nlspn_gconv_wgrad_bf16x3_workspace_bytes(int stride, int Cs, int Cl, int B, int Hs, int Ws, int Hl, int Wl) {
+    if (gw_check_shape(stride, Cs, Cl, B, Hs, Ws, Hl, Wl)) return 0;
+    const long long floats = gw16_choose(stride, Cs, Cl) == kGw16F32 ? gw_plan(stride, Cs, Cl, B, Hs, Ws, Hl, Wl).floats
+                                                                     : gw16_plan(stride, Cs, Cl, B, Hs, Ws, Hl, Wl).floats;
+    return (size_t)floats * sizeof(float);
+}
+
+int nlspn_gconv_wgrad_bf16x3(int stride, const float *s, int Cs, const float *l0, int c0, const float *l1, int c1,
+                             float *dw, float *db, int bias_from_large, float scale, void *workspace,
+                             int64_t workspace_bytes, int B, int Hs, int Ws, int Hl, int Wl, void *stream) {
+    NLSPN_TRY(gw_check_call(stride, s, Cs, l0, c0, l1, c1, dw, db, bias_from_large, workspace, B, Hs, Ws, Hl, Wl));
+    const int Cl = c0 + c1;
+    // both channel counts <= 16: the one-wave f32 kernel, bit for bit (its cost is staging, not MFMA)
+    if (gw16_choose(stride, Cs, Cl) == kGw16F32)
+        return nlspn_gconv_wgrad(stride, s, Cs, l0, c0, l1, c1, dw, db, bias_from_large, scale, workspace, workspace_bytes,
+                                 B, Hs, Ws, Hl, Wl, stream);
+    const Gw16Plan pl = gw16_plan(stride, Cs, Cl, B, Hs, Ws, Hl, Wl);
+    NLSPN_TRY(gw_check_workspace(workspace_bytes, pl.floats));
+    // (the kernel's per-thread staging offsets are 32 bits: a pass's 8 channel planes and one window row)
+    if ((long long)pl.mtiles * pl.ntiles * pl.nsl > 0x7fffffffLL || (long long)Hs * Ws > (1LL << 27) || (long long)Hl * Wl > (1LL << 27))
+        return fail(NLSPN_EINVAL, "gconv wgrad: problem too large");
+    const void *fn = gw16_kernel_of(pl.g);
+    if (!fn) return fail(NLSPN_EUNSUPPORTED, "gconv wgrad bf16x3: no kernel for tiling %d", pl.tiling);
+    GwgradArgs a = gw_args(s, Cs, l0, c0, l1, c1, workspace, B, Hs, Ws, Hl, Wl, pl);
+    return gw_launch(fn, pl.g.nthr(), pl.g.lds_bytes(), pl.g.nt(), a, pl, dw, db, bias_from_large, scale, stream,
+                     NLSPN_GW_LABELS("nlspn_gconv_wgrad_bf16x3"));
 }
 
 int nlspn_gconv_dgrad(int layer, const float *g, int cg, const float *wpk, const float *ysave, const float *add0,
@@ -405,17 +403,15 @@ int nlspn_gconv_dgrad(int layer, const float *g, int cg, const float *wpk, const
     a.scale = scale; a.act = act; a.in_div = 1.f;
     a.c0 = cg; a.cin_pad = (cg + kGcCP - 1) / kGcCP * kGcCP;
     a.B = B; a.Hi = Hg; a.Wi = Wg;
-    if (p.mode == kGcT2) { a.Ho = 2 * Hg; a.Wo = 2 * Wg; }
+    if (p.mode == kGcT2) gc_out_size(kGcT2, Hg, Wg, a.Ho, a.Wo);
     else { a.Ho = Ho; a.Wo = Wo; }
     a.ohs = Ho; a.ows = Wo;
     a.cout = cout;
     a.co_tiles = (cout + p.wgco - 1) / p.wgco;
-    NLSPN_TRY(gc_tile(p, a));
-    const long long nwg = (long long)(p.mode == kGcT2 ? 4 : 1) * a.co_tiles * B * a.nbands * a.tpb;
+    NLSPN_TRY(gc_tile(p, a, "gconv"));
+    const long long nwg = gc_wgs(p, a);
     if (nwg > 0x7fffffffLL || (long long)cg * Hg * Wg * 4 > 0x7fffffffLL) return fail(NLSPN_EINVAL, "gconv dgrad: problem too large");
-    NLSPN_TRY(set_lds_attr(p.fn, p.lds));
-    void *args[] = {&a};
-    return launch_kernel(p.fn, dim3((unsigned)nwg), dim3(kGcNT), args, (size_t)p.lds, as_stream(stream), "nlspn_gconv_dgrad");
+    return gc_launch(p, a, nwg, stream, "nlspn_gconv_dgrad");
 }
 
 int nlspn_gconv_gru_train(int stage, const float *x0, const float *x1, int c1, const float *wpk, const float *bias,
@@ -449,51 +445,19 @@ int nlspn_gconv_gru_gates_backward(int stage, const float *dhn, const float *z, 
                          as_stream(stream), "nlspn_gconv_gru_gates_backward");
 }
 
-}  // extern "C"
-
 // ---------------------------------------------------------------- f16 operands (nlspn_gconv16.h)
-namespace {
-struct Gc16Preset {
-    const void *fn;
-    int mode, wgco, npx, xr, xp, ccb, lds, epi;
-};
-template <int MODE, int WM, int WN, int WGM, int WGN, int XR, int XP, int CCB, int EPI>
-Gc16Preset gc16_preset() {
-    using Cfg = Gc16Cfg<MODE, WM, WN, WGM, WGN, XR, XP, CCB, EPI>;
-    return Gc16Preset{reinterpret_cast<const void *>(&gconv16_kernel<MODE, WM, WN, WGM, WGN, XR, XP, CCB, EPI>), MODE,
-                      Cfg::WGCO, Cfg::NPX, XR, XP, CCB, Cfg::LDS_BYTES, EPI};
-}
-bool gc16_get(int layer, Gc16Preset &p) {
-    switch (layer) {
-#define NLSPN_GC16_CASE(id, ...) \
-    case id: p = gc16_preset<__VA_ARGS__>(); return true;
-        NLSPN_GC16_CONFIGS(NLSPN_GC16_CASE)
-        default: return false;
-    }
-}
-}  // namespace
-extern "C" {
-
 int nlspn_gconv16_pack_layout(int layer, int *co_tile, int *cin_chunk, int *transposed) {
-    if (layer == NLSPN_GC16_S2_SMALL) {  // the module's own f32 weight layout
-        if (co_tile) *co_tile = 0;
-        if (cin_chunk) *cin_chunk = 1;
-        if (transposed) *transposed = 0;
-        return NLSPN_OK;
-    }
-    Gc16Preset p;
-    if (!gc16_get(layer, p)) return fail(NLSPN_EINVAL, "gconv16: preset %d is not an f16 preset (NLSPN_GC16_*)", layer);
-    if (co_tile) *co_tile = p.wgco;
-    if (cin_chunk) *cin_chunk = 8 * p.ccb;
-    if (transposed) *transposed = p.mode == kGcT2;
-    return NLSPN_OK;
+    GcPreset p;
+    const bool small = layer == NLSPN_GC16_S2_SMALL;  // (the module's own f32 weight layout)
+    if (!small && !gc16_get(layer, p)) return fail(NLSPN_EINVAL, "gconv16: preset %d is not an f16 preset (NLSPN_GC16_*)", layer);
+    return gc_pack_layout(small ? nullptr : &p, co_tile, cin_chunk, transposed);
 }
 
 int nlspn_gconv16(int layer, const void *x0, int c0, const void *x1, int c1, const void *wpk, const float *bias,
                   void *y16, float *y32, const float *h, float *zb, void *rh16, float *qxb, float *hout32,
                   void *hout16, int B, int Hi, int Wi, int cout, int ohs, int ows, int act, float in_div, int hc,
                   void *stream) {
-    Gc16Preset p{};
+    GcPreset p{};
     const bool small = layer == NLSPN_GC16_S2_SMALL;
     if (!small && !gc16_get(layer, p))
         return fail(NLSPN_EINVAL, "gconv16: preset %d is not an f16 preset (NLSPN_GC16_*)", layer);
@@ -502,9 +466,9 @@ int nlspn_gconv16(int layer, const void *x0, int c0, const void *x1, int c1, con
     if (!x0 || !wpk || !bias) return fail(NLSPN_EINVAL, "gconv16: null input, weights or bias");
     if (act < NLSPN_GC_ACT_NONE || act > NLSPN_GC_ACT_TANH) return fail(NLSPN_EINVAL, "gconv16: activation %d", act);
     // (a chunk of channel blocks is staged from one source, through one descriptor)
-    if (!small && c1 > 0 && c0 % (8 * p.ccb) != 0)
+    if (!small && c1 > 0 && c0 % p.cc != 0)
         return fail(NLSPN_EINVAL, "gconv16: a channel chunk would straddle the two sources (c0 = %d, not a multiple of %d)",
-                    c0, 8 * p.ccb);
+                    c0, p.cc);
     if (!small && in_div != 1.f)
         return fail(NLSPN_EINVAL, "gconv16: in_div %g needs the NLSPN_GC16_S2_SMALL preset", (double)in_div);
     const bool gru = !small && (p.epi == kGcEpiGru1 || p.epi == kGcEpiGru2), gru1 = !small && p.epi == kGcEpiGru1;
@@ -514,9 +478,7 @@ int nlspn_gconv16(int layer, const void *x0, int c0, const void *x1, int c1, con
     a.h = h; a.zb = zb; a.rh16 = static_cast<_Float16 *>(rh16); a.qxb = qxb;
     a.hout32 = hout32; a.hout16 = static_cast<_Float16 *>(hout16);
     a.c0 = c0; a.c1 = c1; a.B = B; a.Hi = Hi; a.Wi = Wi; a.cout = cout; a.act = act; a.in_div = in_div; a.hc = hc;
-    if (small || p.mode == kGcS2) { a.Ho = (Hi - 1) / 2 + 1; a.Wo = (Wi - 1) / 2 + 1; }
-    else if (p.mode == kGcS1) { a.Ho = Hi; a.Wo = Wi; }
-    else { a.Ho = 2 * Hi; a.Wo = 2 * Wi; }
+    gc_out_size(small ? kGcS2 : p.mode, Hi, Wi, a.Ho, a.Wo);
     a.ohs = gru ? a.Ho : ohs;
     a.ows = gru ? a.Wo : ows;
     if (gru) {
@@ -535,33 +497,22 @@ int nlspn_gconv16(int layer, const void *x0, int c0, const void *x1, int c1, con
         if (c1 != 0 || cout != 16 || c0 * 16 * 9 > kGsMaxW)
             return fail(NLSPN_EINVAL, "gconv16 small: cin %d (c1 %d), cout %d outside the VALU kernel's range (cout 16, "
                         "cin <= 16)", c0, c1, cout);
-        const long long npix = (long long)B * a.ohs * a.ows;
-        const unsigned grid = (unsigned)std::min<long long>((npix + kGsNT - 1) / kGsNT, 1 << 20);
         const float *wf = static_cast<const float *>(wpk);
         void *args[] = {&a, &wf};
-        return launch_kernel(reinterpret_cast<const void *>(&gsmall16_kernel<16>), dim3(grid), dim3(kGsNT), args, 0,
-                             as_stream(stream), "nlspn_gconv16 small");
+        return launch_kernel(reinterpret_cast<const void *>(&gsmall16_kernel<16>), dim3(gs_grid((long long)B * a.ohs * a.ows)),
+                             dim3(kGsNT), args, 0, as_stream(stream), "nlspn_gconv16 small");
     }
+    const int ccb = p.cc / 8;  // the 8-channel blocks of a chunk
     a.nb0 = (c0 + 7) / 8;
     a.nb1 = (c1 + 7) / 8;
-    a.nbp = (a.nb0 + a.nb1 + p.ccb - 1) / p.ccb * p.ccb;
+    a.nbp = (a.nb0 + a.nb1 + ccb - 1) / ccb * ccb;
     a.co_tiles = (cout + p.wgco - 1) / p.wgco;
-    {
-        GcTiling t;
-        const bool ok = nlspn::gc_tile(GcGeo{p.mode, p.wgco, p.npx, p.xr, p.xp}, p.mode == kGcT2 ? Hi : a.Ho,
-                                       p.mode == kGcT2 ? Wi : a.Wo, t);
-        a.gh = t.gh; a.gw = t.gw; a.bw = t.bw; a.nbands = t.nbands; a.tpb = t.tpb; a.npx = t.npx;
-        if (!ok)
-            return fail(NLSPN_EUNSUPPORTED, "gconv16: a tile of a %d-wide band spans more than %d window rows", a.bw, p.xr);
-    }
-    long long nwg = (long long)(p.mode == kGcT2 ? 4 : 1) * a.co_tiles * B * a.nbands * a.tpb;
-    if (gru1) nwg = gc_gru1_wgs(a.hc, p.wgco, a.co_tiles, gc_rest_count(a.B, a.nbands, a.tpb));
+    NLSPN_TRY(gc_tile(p, a, "gconv16"));
+    const long long nwg = gc_wgs(p, a);
     // (one image's channel blocks of a source within a 32-bit buffer descriptor)
     if (nwg > 0x7fffffffLL || (long long)std::max(a.nb0, a.nb1) * Hi * Wi * 16 > 0x7fffffffLL)
         return fail(NLSPN_EINVAL, "gconv16: problem too large");
-    NLSPN_TRY(set_lds_attr(p.fn, p.lds));
-    void *args[] = {&a};
-    return launch_kernel(p.fn, dim3((unsigned)nwg), dim3(kGcNT), args, (size_t)p.lds, as_stream(stream), "nlspn_gconv16");
+    return gc_launch(p, a, nwg, stream, "nlspn_gconv16");
 }
 
 }  // extern "C"

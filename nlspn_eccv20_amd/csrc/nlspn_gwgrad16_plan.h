@@ -7,13 +7,7 @@
 // launcher call these very functions.
 #pragma once
 
-#ifndef NLSPN_HD
-#if defined(__HIPCC__)
-#define NLSPN_HD __host__ __device__
-#else
-#define NLSPN_HD
-#endif
-#endif
+#include "nlspn_gwgrad_plan.h"  // NLSPN_HD; gw_split and the bias slices both entries share
 
 namespace nlspn {
 #pragma GCC visibility push(hidden)
@@ -37,7 +31,6 @@ constexpr int kGw16LdsBudget = 160 * 1024;
 #define NLSPN_GW16_TARGET_WGS 256
 #endif
 constexpr int kGw16TargetWgs = NLSPN_GW16_TARGET_WGS;  // K slices x tiles aimed at (a constant, not the device's CU count)
-constexpr int kGw16MaxBiasSlices = 64;           // as the f32 entry's bias partials
 static_assert((kGw16AP * 2) % 64 == 32 && (kGw16BP * 2) % 64 == 32, "bank rule");
 static_assert(kGw16AP % 8 == 0 && kGw16BP % 8 == 0 && kGw16BW % 8 == 0, "16-byte fragments");
 
@@ -115,34 +108,14 @@ NLSPN_HD inline Gw16Unit gw16_unit(int u, int nbands, int bw, int Hs, int Ws) {
 }
 
 // ---- the plan of one call, a pure function of the shape (the shape is validated by the caller)
-struct Gw16Plan {
+struct Gw16Plan : GwSplit {
     int tiling;
     Gw16Geo g;
-    int mtiles, ntiles, bw, nbands, units, ups, nsl, nsb;
-    long long slab, bias_off, floats;  // slab floats; the bias partials' offset; the workspace's floats
 };
 NLSPN_HD inline Gw16Plan gw16_plan(int stride, int Cs, int Cl, int B, int Hs, int Ws, int Hl, int Wl) {
-    Gw16Plan p{};
-    p.tiling = gw16_choose(stride, Cs, Cl);
-    p.g = gw16_geo(p.tiling);
-    const int mt = p.g.mt(), nt = p.g.nt();
-    p.mtiles = (Cs + mt - 1) / mt;
-    p.ntiles = (Cl + nt - 1) / nt;
-    p.nbands = (Ws + kGw16BW - 1) / kGw16BW;
-    p.bw = (Ws + p.nbands - 1) / p.nbands;
-    p.units = B * Hs * p.nbands;
-    const int tiles = p.mtiles * p.ntiles;
-    int nsl = (kGw16TargetWgs + tiles - 1) / tiles;
-    nsl = nsl < p.units ? nsl : p.units;
-    nsl = nsl > 1 ? nsl : 1;
-    p.ups = (p.units + nsl - 1) / nsl;
-    p.nsl = (p.units + p.ups - 1) / p.ups;
-    p.slab = (long long)p.mtiles * mt * p.ntiles * nt * 9;
-    const long long nb = ((long long)B * Hl * Wl + 16383) / 16384;
-    p.nsb = (int)(nb < 1 ? 1 : nb > kGw16MaxBiasSlices ? kGw16MaxBiasSlices : nb);
-    p.bias_off = p.slab * p.nsl;
-    p.floats = p.bias_off + (long long)p.nsb * (Cs > Cl ? Cs : Cl);
-    return p;
+    const int tiling = gw16_choose(stride, Cs, Cl);
+    const Gw16Geo g = gw16_geo(tiling);
+    return Gw16Plan{gw_split(g.mt(), g.nt(), kGw16BW, kGw16TargetWgs, Cs, Cl, B, Hs, Ws, Hl, Wl), tiling, g};
 }
 
 #pragma GCC visibility pop

@@ -53,6 +53,8 @@ everything else of the backward is the same launches, and ``stats["wgrad_x3"]`` 
 from __future__ import annotations
 
 import ctypes
+import functools
+import typing
 
 import torch
 import torch.nn as nn
@@ -74,48 +76,98 @@ _T_TAPS = [[(ky, kx) for ky in ((0, 2) if py else (1,)) for kx in ((0, 2) if px 
            for py in (0, 1) for px in (0, 1)]
 
 
-def _layout(layer):
+class _Family(typing.NamedTuple):
+    """A preset family: the pack-layout query of the C ABI, the weight dtype and the inner
+    channel block (the f32 kernels read [co_tile][cin_pad][tap][co]; the f16 ones the same with
+    the input channels in blocks of 8 innermost, [co_tile][cin_pad/8][tap][co][8]), and its
+    presets by layer kind (s2_c16 / t2_c16: at most 16 output channels; small: the VALU kernel)."""
+    query: str
+    dtype: torch.dtype
+    block: int
+    s2: int
+    s2_c16: int
+    t2: int
+    t2_c16: int
+    small: int
+    gru1: int
+    gru2: int
+
+
+_F32 = _Family("nlspn_gconv_pack_layout", torch.float32, 1, GC_S2, GC_S2_C16, GC_T2, GC_T2_C16, GC_S2_SMALL, GC_GRU1, GC_GRU2)
+# (the f16 stride-2 conv has one tiling for every width)
+_F16 = _Family("nlspn_gconv16_pack_layout", torch.float16, 8, GC16_S2, GC16_S2, GC16_T2, GC16_T2_C16, GC16_S2_SMALL,
+               GC16_GRU1, GC16_GRU2)
+_TAPS = [[(ky, kx) for ky in range(3) for kx in range(3)]]  # a conv: one part, all nine taps
+
+
+def _layout_of(fam, layer):
+    """(output-channel tile, input-channel chunk, transposed) of a preset of family ``fam``."""
     lib = _lib.get()  # a query: no device, no launch
     co, cc, tr = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(lib.nlspn_gconv_pack_layout(layer, ctypes.byref(co), ctypes.byref(cc), ctypes.byref(tr)))
+    _lib.check(getattr(lib, fam.query)(layer, ctypes.byref(co), ctypes.byref(cc), ctypes.byref(tr)))
     return co.value, cc.value, bool(tr.value)
 
 
-def pack_conv(weight: torch.Tensor, bias: torch.Tensor, layer: int):
-    """(Cout, Cin, 3, 3) conv weight -> [co_tile][cin_pad][9][co_tile_width]; bias padded."""
-    wgco, cc, tr = _layout(layer)
-    assert not tr
-    cout, cin = weight.shape[:2]
-    ct = (cout + wgco - 1) // wgco
-    cp = (cin + cc - 1) // cc * cc
-    w = torch.zeros((ct * wgco, cp, 9), device=weight.device, dtype=torch.float32)
-    w[:cout, :cin] = weight.detach().float().reshape(cout, cin, 9)
-    w = w.reshape(ct, wgco, cp, 9).permute(0, 2, 3, 1).contiguous()
-    b = torch.zeros(ct * wgco, device=weight.device, dtype=torch.float32)
+def _pad_bias(bias, cout, n, device):
+    b = torch.zeros(n, device=device, dtype=torch.float32)
     if bias is not None:
         b[:cout] = bias.detach().float()
-    return w.reshape(-1), b
+    return b
 
 
-def pack_convt(weight: torch.Tensor, bias: torch.Tensor, layer: int):
-    """(Cin, Cout, 3, 3) transposed-conv weight -> per output phase [co_tile][cin_pad][ntap][width],
-    the phases one after another; bias padded."""
-    wgco, cc, tr = _layout(layer)
-    assert tr
-    cin, cout = weight.shape[:2]
+def _pack(fam, transposed, weight, bias, layer):
+    """The packed weights and padded f32 bias of a conv ((Cout, Cin, 3, 3)) or transposed conv
+    ((Cin, Cout, 3, 3)) for a preset of family ``fam``: converted to the family's dtype first
+    (half: one rounding to nearest-even), then per part (a conv: one; a transposed conv: its
+    four output phases, one after another) [co_tile][cin_pad / block][tap][co][block]."""
+    wgco, cc, tr = _layout_of(fam, layer)
+    assert tr == transposed
+    dtype, cb = fam.dtype, fam.block
+    wd = weight.detach().to(dtype)
+    if transposed:
+        wd = wd.transpose(0, 1)
+    cout, cin = wd.shape[:2]
     ct = (cout + wgco - 1) // wgco
     cp = (cin + cc - 1) // cc * cc
-    wd = weight.detach().float()
     parts = []
-    for taps in _T_TAPS:
-        w = torch.zeros((ct * wgco, cp, len(taps)), device=weight.device, dtype=torch.float32)
+    for taps in (_T_TAPS if transposed else _TAPS):
+        w = torch.zeros((ct * wgco, cp, len(taps)), device=weight.device, dtype=dtype)
         for t, (ky, kx) in enumerate(taps):
-            w[:cout, :cin, t] = wd[:, :, ky, kx].t()
-        parts.append(w.reshape(ct, wgco, cp, len(taps)).permute(0, 2, 3, 1).contiguous().reshape(-1))
-    b = torch.zeros(ct * wgco, device=weight.device, dtype=torch.float32)
-    if bias is not None:
-        b[:cout] = bias.detach().float()
-    return torch.cat(parts), b
+            w[:cout, :cin, t] = wd[:, :, ky, kx]
+        parts.append(w.reshape(ct, wgco, cp // cb, cb, len(taps)).permute(0, 2, 4, 1, 3).contiguous().reshape(-1))
+    return torch.cat(parts), _pad_bias(bias, cout, ct * wgco, weight.device)
+
+
+def _unpack(fam, transposed, w, cout, cin, layer):
+    """Inverse of _pack: the module's (Cout, Cin, 3, 3) or (Cin, Cout, 3, 3) tensor, in w's dtype."""
+    wgco, cc, _ = _layout_of(fam, layer)
+    cb = fam.block
+    ct, cp = (cout + wgco - 1) // wgco, (cin + cc - 1) // cc * cc
+    out = torch.zeros((cout, cin, 3, 3), device=w.device, dtype=w.dtype)
+    o = 0
+    for taps in (_T_TAPS if transposed else _TAPS):
+        n = ct * cp * len(taps) * wgco
+        part = w[o:o + n].reshape(ct, cp // cb, len(taps), wgco, cb).permute(0, 3, 1, 4, 2).reshape(ct * wgco, cp, len(taps))
+        for t, (ky, kx) in enumerate(taps):
+            out[:, :, ky, kx] = part[:cout, :cin, t]
+        o += n
+    return out.transpose(0, 1).contiguous() if transposed else out
+
+
+# the public packers: (weight, bias, layer) -> (packed weights, padded bias), and their inverses
+# (w, cout, cin, layer) / transposed (w, cin, cout, layer) -> the module's tensor
+_layout, _layout16 = functools.partial(_layout_of, _F32), functools.partial(_layout_of, _F16)
+pack_conv, pack_convt = functools.partial(_pack, _F32, False), functools.partial(_pack, _F32, True)
+pack_conv16, pack_convt16 = functools.partial(_pack, _F16, False), functools.partial(_pack, _F16, True)
+unpack_conv, unpack_conv16 = functools.partial(_unpack, _F32, False), functools.partial(_unpack, _F16, False)
+
+
+def unpack_convt(w, cin, cout, layer):
+    return _unpack(_F32, True, w, cout, cin, layer)
+
+
+def unpack_convt16(w, cin, cout, layer):
+    return _unpack(_F16, True, w, cout, cin, layer)
 
 
 def _conv_of(seq):
@@ -136,6 +188,37 @@ class _Layer:
         self.conv, self.adj, self.dg = conv, None, None
 
 
+def _make_layer(fam, conv, act, valu):
+    """The packed layer of a stride-2 conv / transposed conv module in family ``fam``: at most 16
+    output channels take the *_C16 preset; with ``valu`` a 1 / 9 -> 16 conv (16 output, at most
+    16 input channels) takes the VALU kernel, which reads the module's own f32 weight layout."""
+    transposed, narrow = isinstance(conv, nn.ConvTranspose2d), conv.out_channels <= 16
+    if valu and not transposed and conv.out_channels == 16 and conv.in_channels <= 16:
+        return _Layer(fam.small, conv.weight.detach().float().contiguous(), conv.bias.detach().float().contiguous(),
+                      conv.in_channels, conv.out_channels, act, conv)
+    kind = (fam.t2_c16 if narrow else fam.t2) if transposed else (fam.s2_c16 if narrow else fam.s2)
+    w, b = _pack(fam, transposed, conv.weight, conv.bias, kind)
+    return _Layer(kind, w, b, conv.in_channels, conv.out_channels, act, conv)
+
+
+def _chain_layers(fam, seq, last_act=None):
+    """The layers of a module chain (the first conv may take the VALU kernel); last_act: the
+    activation of the last one when it is not the module's ReLU."""
+    out = [_make_layer(fam, _conv_of(s), ACT_RELU if _has_relu(s) else ACT_NONE, i == 0) for i, s in enumerate(seq)]
+    if last_act is not None:
+        out[-1].act = last_act
+    return out
+
+
+def _gru_layers(fam, g):
+    """The ConvGRU's two launches: [convz; convr; convq] over (h, x), then convq's h half over r h."""
+    hc = g.convz.out_channels
+    w1 = torch.cat([g.convz.weight, g.convr.weight, g.convq.weight], 0)
+    b1 = torch.cat([g.convz.bias, g.convr.bias, g.convq.bias], 0)
+    return (_Layer(fam.gru1, *_pack(fam, False, w1, b1, fam.gru1), 2 * hc, 3 * hc, ACT_NONE),
+            _Layer(fam.gru2, *_pack(fam, False, g.convq.weight[:, :hc], g.convq.bias, fam.gru2), hc, hc, ACT_NONE))
+
+
 def pack_adjoint(conv):
     """(preset, packed weights) of the data gradient of a stride-2 conv / transposed conv
     module: the adjoint of a conv is the transposed conv of the same (Cout, Cin, 3, 3) tensor,
@@ -153,28 +236,6 @@ def pack_adjoint_s1(weight):
     return pack_conv(weight.detach().transpose(0, 1).flip(2, 3), None, GC_DG_S1)[0]
 
 
-def unpack_conv(w, cout, cin, layer):
-    """Inverse of pack_conv: the (cout, cin, 3, 3) tensor of a packed conv weight."""
-    wgco, cc, _ = _layout(layer)
-    ct, cp = (cout + wgco - 1) // wgco, (cin + cc - 1) // cc * cc
-    return w.reshape(ct, cp, 9, wgco).permute(0, 3, 1, 2).reshape(ct * wgco, cp, 3, 3)[:cout, :cin]
-
-
-def unpack_convt(w, cin, cout, layer):
-    """Inverse of pack_convt: the (cin, cout, 3, 3) tensor of a packed transposed-conv weight."""
-    wgco, cc, _ = _layout(layer)
-    ct, cp = (cout + wgco - 1) // wgco, (cin + cc - 1) // cc * cc
-    out = torch.zeros((cin, cout, 3, 3), device=w.device, dtype=w.dtype)
-    o = 0
-    for taps in _T_TAPS:
-        n = ct * cp * len(taps) * wgco
-        part = w[o:o + n].reshape(ct, cp, len(taps), wgco).permute(0, 3, 1, 2).reshape(ct * wgco, cp, len(taps))
-        for t, (ky, kx) in enumerate(taps):
-            out[:, :, ky, kx] = part[:cout, :cin, t].t()
-        o += n
-    return out
-
-
 # ---------------------------------------------------------------------- f16 operands (nlspn_gconv16.h)
 def to_c8(x: torch.Tensor) -> torch.Tensor:
     """(B, C, H, W) -> the kernels' c8 layout (B, ceil(C/8), H, W, 8) in half, pad channels zero;
@@ -190,74 +251,6 @@ def from_c8(y: torch.Tensor, C: int) -> torch.Tensor:
     """Inverse of to_c8: the (B, C, H, W) half tensor of a c8 tensor."""
     B, nb, H, W, _ = y.shape
     return y.permute(0, 1, 4, 2, 3).reshape(B, nb * 8, H, W)[:, :C].contiguous()
-
-
-def _layout16(layer):
-    lib = _lib.get()  # a query: no device, no launch
-    co, cc, tr = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(lib.nlspn_gconv16_pack_layout(layer, ctypes.byref(co), ctypes.byref(cc), ctypes.byref(tr)))
-    return co.value, cc.value, bool(tr.value)
-
-
-def _pad_bias(bias, cout, n, device):
-    b = torch.zeros(n, device=device, dtype=torch.float32)
-    if bias is not None:
-        b[:cout] = bias.detach().float()
-    return b
-
-
-def pack_conv16(weight: torch.Tensor, bias: torch.Tensor, layer: int):
-    """(Cout, Cin, 3, 3) conv weight -> half [co_tile][cin_pad/8][9][co_tile_width][8], rounded to
-    nearest-even once; bias f32, padded."""
-    wgco, cc, tr = _layout16(layer)
-    assert not tr
-    cout, cin = weight.shape[:2]
-    ct = (cout + wgco - 1) // wgco
-    cp = (cin + cc - 1) // cc * cc
-    w = torch.zeros((ct * wgco, cp, 9), device=weight.device, dtype=torch.float16)
-    w[:cout, :cin] = weight.detach().reshape(cout, cin, 9).to(torch.float16)
-    w = w.reshape(ct, wgco, cp // 8, 8, 9).permute(0, 2, 4, 1, 3).contiguous()
-    return w.reshape(-1), _pad_bias(bias, cout, ct * wgco, weight.device)
-
-
-def pack_convt16(weight: torch.Tensor, bias: torch.Tensor, layer: int):
-    """(Cin, Cout, 3, 3) transposed-conv weight -> half, per output phase
-    [co_tile][cin_pad/8][ntap][width][8], the phases one after another; bias f32, padded."""
-    wgco, cc, tr = _layout16(layer)
-    assert tr
-    cin, cout = weight.shape[:2]
-    ct = (cout + wgco - 1) // wgco
-    cp = (cin + cc - 1) // cc * cc
-    wd = weight.detach().to(torch.float16)
-    parts = []
-    for taps in _T_TAPS:
-        w = torch.zeros((ct * wgco, cp, len(taps)), device=weight.device, dtype=torch.float16)
-        for t, (ky, kx) in enumerate(taps):
-            w[:cout, :cin, t] = wd[:, :, ky, kx].t()
-        parts.append(w.reshape(ct, wgco, cp // 8, 8, len(taps)).permute(0, 2, 4, 1, 3).contiguous().reshape(-1))
-    return torch.cat(parts), _pad_bias(bias, cout, ct * wgco, weight.device)
-
-
-def unpack_conv16(w, cout, cin, layer):
-    """Inverse of pack_conv16: the (cout, cin, 3, 3) half tensor of a packed conv weight."""
-    wgco, cc, _ = _layout16(layer)
-    ct, cp = (cout + wgco - 1) // wgco, (cin + cc - 1) // cc * cc
-    return w.reshape(ct, cp // 8, 9, wgco, 8).permute(0, 3, 1, 4, 2).reshape(ct * wgco, cp, 3, 3)[:cout, :cin]
-
-
-def unpack_convt16(w, cin, cout, layer):
-    """Inverse of pack_convt16: the (cin, cout, 3, 3) half tensor of a packed transposed-conv weight."""
-    wgco, cc, _ = _layout16(layer)
-    ct, cp = (cout + wgco - 1) // wgco, (cin + cc - 1) // cc * cc
-    out = torch.zeros((cin, cout, 3, 3), device=w.device, dtype=w.dtype)
-    o = 0
-    for taps in _T_TAPS:
-        n = ct * cp * len(taps) * wgco
-        part = w[o:o + n].reshape(ct, cp // 8, len(taps), wgco, 8).permute(0, 3, 1, 4, 2).reshape(ct * wgco, cp, len(taps))
-        for t, (ky, kx) in enumerate(taps):
-            out[:, :, ky, kx] = part[:cout, :cin, t].t()
-        o += n
-    return out
 
 
 class _ChainFn(torch.autograd.Function):
@@ -388,12 +381,6 @@ class GruConvs:
         return w.is_cuda and w.dtype == torch.float32
 
     @staticmethod
-    def _raw(layer, conv, act):
-        """A narrow layer for the VALU kernel: the module's own weight layout."""
-        return _Layer(layer, conv.weight.detach().float().contiguous(), conv.bias.detach().float().contiguous(),
-                      conv.in_channels, conv.out_channels, act, conv)
-
-    @staticmethod
     def _pack_adjoints(model, packed):
         with torch.no_grad():
             for L in packed["dep"] + packed["aff"] + packed["dec"]:
@@ -411,30 +398,12 @@ class GruConvs:
                 self._pack_adjoints(model, e[1])
             return e[1]
         with torch.no_grad():
-            enc = lambda seq: [_Layer(GC_S2_C16 if _conv_of(s).out_channels <= 16 else GC_S2,  # noqa: E731
-                                      *pack_conv(_conv_of(s).weight, _conv_of(s).bias,
-                                                 GC_S2_C16 if _conv_of(s).out_channels <= 16 else GC_S2),
-                                      _conv_of(s).in_channels, _conv_of(s).out_channels,
-                                      ACT_RELU if _has_relu(s) else ACT_NONE, _conv_of(s)) for s in seq]
-            dep = enc(list(model.encode_dep))
-            aff = enc(list(model.encode_aff)[:3])
-            # the first (1 / 9 -> 16 channel) convs on the VALU kernel
-            for lst, seq in ((dep, model.encode_dep), (aff, model.encode_aff)):
-                c = _conv_of(seq[0])
-                if c.out_channels == 16 and c.in_channels <= 16:
-                    lst[0] = self._raw(GC_S2_SMALL, c, lst[0].act)
-            aff[-1].act = ACT_TANH  # encode_aff's Tanh (:131)
-            dec = [_Layer(GC_T2_C16 if _conv_of(s).out_channels <= 16 else GC_T2,
-                          *pack_convt(_conv_of(s).weight, _conv_of(s).bias,
-                                      GC_T2_C16 if _conv_of(s).out_channels <= 16 else GC_T2),
-                          _conv_of(s).in_channels, _conv_of(s).out_channels,
-                          ACT_RELU if _has_relu(s) else ACT_NONE, _conv_of(s)) for s in model.decode_aff]
+            dep = _chain_layers(_F32, list(model.encode_dep))
+            aff = _chain_layers(_F32, list(model.encode_aff)[:3], ACT_TANH)  # encode_aff's Tanh (:131)
+            dec = _chain_layers(_F32, list(model.decode_aff))
             g = model.GRU
-            w1 = torch.cat([g.convz.weight, g.convr.weight, g.convq.weight], 0)
-            b1 = torch.cat([g.convz.bias, g.convr.bias, g.convq.bias], 0)
+            gru1, gru2 = _gru_layers(_F32, g)
             hc = g.convz.out_channels
-            gru1 = _Layer(GC_GRU1, *pack_conv(w1, b1, GC_GRU1), 2 * hc, 3 * hc, ACT_NONE)
-            gru2 = _Layer(GC_GRU2, *pack_conv(g.convq.weight[:, :hc], g.convq.bias, GC_GRU2), hc, hc, ACT_NONE)
         packed = {"dep": dep, "aff": aff, "dec": dec, "gru1": gru1, "gru2": gru2, "hc": hc,
                   "gru_params": [g.convz.weight, g.convz.bias, g.convr.weight, g.convr.bias, g.convq.weight, g.convq.bias]}
         if torch.is_grad_enabled():
@@ -455,33 +424,10 @@ class GruConvs:
             raise NotImplementedError("gru_precision = 'fp16' needs the reference's GRU-mode layers (1 / 9 -> 16 first "
                                       "encoder convs, at least two decoder layers)")
         with torch.no_grad():
-            def enc(seq, last_act):
-                out = []
-                for i, s in enumerate(seq):
-                    c = _conv_of(s)
-                    act = last_act if i == len(seq) - 1 and last_act is not None else \
-                        (ACT_RELU if _has_relu(s) else ACT_NONE)
-                    if i == 0 and c.out_channels == 16 and c.in_channels <= 16:
-                        out.append(self._raw(GC16_S2_SMALL, c, act))
-                    else:
-                        out.append(_Layer(GC16_S2, *pack_conv16(c.weight, c.bias, GC16_S2), c.in_channels,
-                                          c.out_channels, act, c))
-                return out
-            dec = []
-            for s in list(model.decode_aff)[:-1]:
-                c = _conv_of(s)
-                kind = GC16_T2_C16 if c.out_channels <= 16 else GC16_T2
-                dec.append(_Layer(kind, *pack_convt16(c.weight, c.bias, kind), c.in_channels, c.out_channels,
-                                  ACT_RELU if _has_relu(s) else ACT_NONE, c))
-            g = model.GRU
-            hc = P["hc"]
-            w1 = torch.cat([g.convz.weight, g.convr.weight, g.convq.weight], 0)
-            b1 = torch.cat([g.convz.bias, g.convr.bias, g.convq.bias], 0)
-            P["f16"] = {"dep": enc(list(model.encode_dep), None), "aff": enc(list(model.encode_aff)[:3], ACT_TANH),
-                        "dec": dec,
-                        "gru1": _Layer(GC16_GRU1, *pack_conv16(w1, b1, GC16_GRU1), 2 * hc, 3 * hc, ACT_NONE),
-                        "gru2": _Layer(GC16_GRU2, *pack_conv16(g.convq.weight[:, :hc], g.convq.bias, GC16_GRU2), hc, hc,
-                                       ACT_NONE)}
+            gru1, gru2 = _gru_layers(_F16, model.GRU)
+            P["f16"] = {"dep": _chain_layers(_F16, list(model.encode_dep)),
+                        "aff": _chain_layers(_F16, list(model.encode_aff)[:3], ACT_TANH),
+                        "dec": _chain_layers(_F16, list(model.decode_aff)[:-1]), "gru1": gru1, "gru2": gru2}
         return P
 
     # ------------------------------------------------------------------ f16 launches (inference)
@@ -639,14 +585,7 @@ class GruConvs:
         """One stride-2 conv / transposed conv module with activation ``act`` on the HIP kernels,
         differentiable: a one-layer chain packed on the spot (tests; the model uses the cached packs)."""
         with torch.no_grad():
-            if isinstance(conv, nn.ConvTranspose2d):
-                kind = GC_T2_C16 if conv.out_channels <= 16 else GC_T2
-                L = _Layer(kind, *pack_convt(conv.weight, conv.bias, kind), conv.in_channels, conv.out_channels, act, conv)
-            elif conv.out_channels == 16 and conv.in_channels <= 16:
-                L = self._raw(GC_S2_SMALL, conv, act)
-            else:
-                kind = GC_S2_C16 if conv.out_channels <= 16 else GC_S2
-                L = _Layer(kind, *pack_conv(conv.weight, conv.bias, kind), conv.in_channels, conv.out_channels, act, conv)
+            L = _make_layer(_F32, conv, act, True)
             L.dg, L.adj = pack_adjoint(conv)
         return self._chain([L], x, in_div=in_div, crop=crop)
 

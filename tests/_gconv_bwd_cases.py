@@ -27,9 +27,10 @@ Guarded operands (GPU): every device operand is a view into a NaN buffer with GU
 both sides (a read outside the operand turns an output into NaN), every output is pre-filled
 with NaN between two runs of SENT that must be intact afterwards.
 
-Mirrors of the planning arithmetic (gc_tiling of gc_tile, gw_plan of the host's gw_plan) only
-state which edge a case hits (the `edges` of a case); tests/test_gconv_bwd_cpu.py checks every
-claim and ties gw_plan to the library's workspace query.
+Mirrors of the planning arithmetic (gc_tiling of gc_tile, gw_plan of csrc/nlspn_gwgrad_plan.h's
+gw_plan) only state which edge a case hits (the `edges` of a case); tests/test_gconv_bwd_cpu.py
+checks every claim and ties gw_plan to the library's workspace query,
+tests/test_gwgrad16_plan_cpu.py compares it field by field with the launcher's function.
 """
 import functools
 import math
@@ -101,7 +102,7 @@ GW_TARGET, GW_BW, GW_MAX_BIAS = 512, 64, 64
 
 
 def gw_plan(stride, Cs, Cl, B, Hs, Ws, Hl, Wl):
-    """gw_plan (csrc/nlspn_gconv_host.hip): the tiling by channel counts, bands, units, slices
+    """gw_plan (csrc/nlspn_gwgrad_plan.h): the tiling by channel counts, bands, units, slices
     and workspace floats of one nlspn_gconv_wgrad call."""
     tiling, mt, nt = ("1222", 64, 32) if stride == 1 else ("2222", 64, 32) if Cl > 16 else \
         ("2241", 128, 16) if Cs > 16 else ("2111", 16, 16)

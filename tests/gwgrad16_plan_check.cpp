@@ -17,6 +17,14 @@
 // that shape only: its plan and its violations (force_bw: a band width the plan would not
 // choose; read_shift: elements added to every read address, as a wrong pitch would), to show
 // that the check is not vacuous.  tests/test_gwgrad16_plan_cpu.py builds and runs it.
+//
+// A first argument "f32" selects the f32 weight gradient's plan (gw_plan, csrc/nlspn_gwgrad_plan.h,
+// the launcher's function; its kernels' LDS addressing is checked on the device, per element):
+//     f32 <stride> <Cs> <Cl> <B> <Hs> <Ws> <Hl> <Wl>
+// prints that shape's plan; "f32" alone sweeps the four f32 tilings x Ws 1..400 x the same
+// (B, Hs) and cropped sizes: the band widths sum to Ws and none is wider than kGwBW, the slices
+// hit every unit exactly once ((nsl - 1) ups < units <= nsl ups), the tiles cover the channels
+// and floats = slab nsl + nsb max(Cs, Cl).
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -209,6 +217,41 @@ Gw16Plan check_shape(const Shape &s, int force_bw = 0, int shift = 0) {
     return p;
 }
 
+// ---- the f32 plan
+long long f32_grids = 0;
+void f32_violation(const Shape &s, const GwPlan &p, const char *detail) {
+    char buf[640];
+    std::snprintf(buf, sizeof buf,
+                  "{\"stride\": %d, \"Cs\": %d, \"Cl\": %d, \"B\": %d, \"Hs\": %d, \"Ws\": %d, \"Hl\": %d, \"Wl\": %d, "
+                  "\"bw\": %d, \"nbands\": %d, \"units\": %d, \"ups\": %d, \"nsl\": %d, \"detail\": \"%s\"}",
+                  s.stride, s.Cs, s.Cl, s.B, s.Hs, s.Ws, s.Hl, s.Wl, p.bw, p.nbands, p.units, p.ups, p.nsl, detail);
+    if (n_viol < 40) shown.push_back(buf);
+    ++n_viol;
+}
+void f32_check_shape(const Shape &s, const GwGeo &want) {
+    const GwPlan p = gw_plan(s.stride, s.Cs, s.Cl, s.B, s.Hs, s.Ws, s.Hl, s.Wl);
+    ++f32_grids;
+    if (p.g.S != want.S || p.g.wm != want.wm || p.g.wgm != want.wgm || p.g.wgn != want.wgn)
+        f32_violation(s, p, "the tiling rule picked another tiling");
+    long long sum = 0;
+    bool widths_ok = p.nbands >= 1 && p.bw >= 1 && p.bw <= kGwBW;
+    for (int i = 0; widths_ok && i < p.nbands; ++i) {
+        const int w = p.bw < s.Ws - i * p.bw ? p.bw : s.Ws - i * p.bw;  // as the kernel cuts band i
+        widths_ok = w >= 1;
+        sum += w;
+    }
+    if (!widths_ok || sum != s.Ws) f32_violation(s, p, "the band widths do not sum to Ws within kGwBW each");
+    if (p.units != s.B * s.Hs * p.nbands) f32_violation(s, p, "units is not B Hs nbands");
+    if (p.nsl < 1 || p.ups < 1 || (long long)(p.nsl - 1) * p.ups >= p.units || (long long)p.nsl * p.ups < p.units)
+        f32_violation(s, p, "the slices do not hit every unit exactly once");
+    if (p.mtiles * p.g.mt() < s.Cs || (p.mtiles - 1) * p.g.mt() >= s.Cs || p.ntiles * p.g.nt() < s.Cl ||
+        (p.ntiles - 1) * p.g.nt() >= s.Cl || p.slab != (long long)p.mtiles * p.g.mt() * p.ntiles * p.g.nt() * 9)
+        f32_violation(s, p, "the tiles do not cover the channels, or the slab is not theirs");
+    if (p.nsb < 1 || p.nsb > kGwMaxBiasSlices || p.bias_off != p.slab * p.nsl ||
+        p.floats != p.slab * p.nsl + (long long)p.nsb * (s.Cs > s.Cl ? s.Cs : s.Cl))
+        f32_violation(s, p, "floats is not slab nsl + nsb max(Cs, Cl)");
+}
+
 void print_shown() {
     std::printf("[");
     for (size_t i = 0; i < shown.size(); ++i) std::printf("%s\n  %s", i ? "," : "", shown[i].c_str());
@@ -216,7 +259,38 @@ void print_shown() {
 }
 }  // namespace
 
+int f32_main(int argc, char **argv) {
+    if (argc >= 10) {
+        int v[8];
+        for (int i = 0; i < 8; ++i) v[i] = std::atoi(argv[i + 2]);
+        const GwPlan p = gw_plan(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
+        std::printf("{\"S\": %d, \"wm\": %d, \"wgm\": %d, \"wgn\": %d, \"mt\": %d, \"nt\": %d, \"nthr\": %d, \"mtiles\": %d, "
+                    "\"ntiles\": %d, \"bw\": %d, \"nbands\": %d, \"units\": %d, \"ups\": %d, \"nsl\": %d, \"nsb\": %d, "
+                    "\"slab\": %lld, \"bias_off\": %lld, \"floats\": %lld}\n",
+                    p.g.S, p.g.wm, p.g.wgm, p.g.wgn, p.g.mt(), p.g.nt(), p.g.nthr(), p.mtiles, p.ntiles, p.bw, p.nbands, p.units,
+                    p.ups, p.nsl, p.nsb, p.slab, p.bias_off, p.floats);
+        return 0;
+    }
+    // the channel counts of each tiling: a last tile with channels past the counts where the tile allows
+    struct Case { GwGeo g; int stride, Cs, Cl; };
+    const Case cases[] = {{{1, 2, 2, 2}, 1, 136, 40}, {{2, 2, 2, 2}, 2, 136, 40}, {{2, 2, 4, 1}, 2, 136, 9}, {{2, 1, 1, 1}, 2, 16, 9}};
+    const int bh[][2] = {{1, 1}, {2, 2}};
+    for (const Case &c : cases)
+        for (int Ws = 1; Ws <= 400; ++Ws) {
+            for (const auto &q : bh) f32_check_shape(Shape{c.stride, c.Cs, c.Cl, q[0], q[1], Ws, c.stride * q[1], c.stride * Ws}, c.g);
+            if (c.stride != 2) continue;
+            if (2 * Ws - 1 >= 1) f32_check_shape(Shape{2, c.Cs, c.Cl, 1, 1, Ws, 1, 2 * Ws - 1}, c.g);
+            if (2 * Ws - 7 >= 1) f32_check_shape(Shape{2, c.Cs, c.Cl, 1, 4, Ws, 1, 2 * Ws - 7}, c.g);
+        }
+    std::printf("{\"grids\": %lld, \"violations\": %lld, \"band_max\": %d, \"target_wgs\": %d, \"bias_slices_max\": %d,\n \"first\": ",
+                f32_grids, n_viol, kGwBW, kGwTargetWgs, kGwMaxBiasSlices);
+    print_shown();
+    std::printf("}\n");
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc >= 2 && std::string(argv[1]) == "f32") return f32_main(argc, argv);
     if (argc >= 9) {
         int v[10] = {0};
         for (int i = 1; i < argc && i <= 10; ++i) v[i - 1] = std::atoi(argv[i]);

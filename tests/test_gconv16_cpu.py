@@ -64,6 +64,16 @@ def test_pack_convt16_inverts_to_the_rounded_weight(cin, cout, layer, co):
     assert not bool(bpk.any())
     assert torch.equal(G.unpack_convt16(wpk, cin, cout, layer), w.half())
     assert int((wpk != 0).sum()) == int((w.half() != 0).sum())
+    # the layout itself: [phase][co_tile][ci / 8][ntap][co][8], the phases (2 py + px) and their taps
+    # in the kernel's order (py = 0 reads ky = 1, py = 1 reads ky = 0, 2; likewise kx); one interior
+    # element and one of the last (partial, where the counts leave one) tile, by an index computed here
+    ct, cp = -(-cout // co), -(-cin // 32) * 32
+    for o, i, ky, kx in ((5, 11, 1, 2), (5, 11, 1, 1), (cout - 1, cin - 1, 2, 0), (cout - 1, cin - 1, 2, 2)):
+        py, px = int(ky != 1), int(kx != 1)
+        phase, ntap, t = 2 * py + px, (2 if py else 1) * (2 if px else 1), (ky // 2) * (2 if px else 1) + kx // 2
+        base = sum((1, 2, 2, 4)[:phase]) * ct * cp * co
+        at = base + ((((o // co) * (cp // 8) + i // 8) * ntap + t) * co + o % co) * 8 + i % 8
+        assert float(wpk[at]) == float(w.half()[i, o, ky, kx])
 
 
 def test_pack_rounds_to_nearest_even_once():

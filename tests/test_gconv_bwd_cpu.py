@@ -152,6 +152,46 @@ def test_adjoint_packers_invert_and_match_the_forward_packers():
     assert torch.equal(G.unpack_conv(G.pack_conv(w, None, G.GC_GRU2)[0], 256, 256, G.GC_GRU2), w)
 
 
+def _convt_tap_slot(ky, kx):
+    """(output phase 2 py + px, taps of the phase, the tap's index in it) in the kernel's order
+    (csrc/nlspn_gconv.h gc_tap): py = 0 reads ky = 1, py = 1 reads ky = 0, 2; likewise kx."""
+    py, px = int(ky != 1), int(kx != 1)
+    return 2 * py + px, (2 if py else 1) * (2 if px else 1), (ky // 2) * (2 if px else 1) + kx // 2
+
+
+@pytest.mark.parametrize("cout,cin,layer,co", [(72, 20, G.GC_S2, 64), (24, 40, G.GC_S2_C16, 16), (192, 40, G.GC_GRU2, 64)])
+def test_pack_conv_puts_each_weight_at_its_place(cout, cin, layer, co):
+    """[co_tile][cin_pad][9][co]: one interior element and one of the last partial tile, by an
+    index computed here (a pack / unpack pair that are wrong together does not pass); padding zero."""
+    w = torch.randn((cout, cin, 3, 3), generator=torch.Generator().manual_seed(cout + cin))
+    wpk, bpk = G.pack_conv(w, None, layer)
+    assert G._layout(layer) == (co, 16, False)
+    ct, cp = -(-cout // co), -(-cin // 16) * 16
+    assert wpk.dtype == torch.float32 and wpk.numel() == ct * cp * 9 * co and bpk.numel() == ct * co and not bool(bpk.any())
+    for o, i, ky, kx in ((5, 3, 1, 2), (cout - 1, cin - 1, 2, 0)):
+        assert float(wpk[(((o // co) * cp + i) * 9 + 3 * ky + kx) * co + o % co]) == float(w[o, i, ky, kx])
+    assert cout % co != 0 or cin % 16 != 0  # (the second element lies in a partial tile)
+    assert int((wpk != 0).sum()) == int((w != 0).sum())
+    assert torch.equal(G.unpack_conv(wpk, cout, cin, layer), w)
+
+
+@pytest.mark.parametrize("cin,cout,layer,co", [(40, 72, G.GC_T2, 64), (20, 8, G.GC_T2_C16, 16)])
+def test_pack_convt_puts_each_weight_at_its_place(cin, cout, layer, co):
+    """[phase][co_tile][cin_pad][ntap][co], the phases and their taps in the kernel's order."""
+    assert G._T_TAPS == [[(1, 1)], [(1, 0), (1, 2)], [(0, 1), (2, 1)], [(0, 0), (0, 2), (2, 0), (2, 2)]]
+    w = torch.randn((cin, cout, 3, 3), generator=torch.Generator().manual_seed(cout + cin))
+    wpk, bpk = G.pack_convt(w, None, layer)
+    assert G._layout(layer) == (co, 16, True)
+    ct, cp = -(-cout // co), -(-cin // 16) * 16
+    assert wpk.dtype == torch.float32 and wpk.numel() == ct * cp * 9 * co and not bool(bpk.any())
+    for o, i, ky, kx in ((5, 3, 1, 2), (5, 3, 1, 1), (cout - 1, cin - 1, 2, 0), (cout - 1, cin - 1, 2, 2)):
+        phase, ntap, t = _convt_tap_slot(ky, kx)
+        base = sum(n for n in (1, 2, 2, 4)[:phase]) * ct * cp * co
+        assert float(wpk[base + (((o // co) * cp + i) * ntap + t) * co + o % co]) == float(w[i, o, ky, kx])
+    assert int((wpk != 0).sum()) == int((w != 0).sum())
+    assert torch.equal(G.unpack_convt(wpk, cin, cout, layer), w)
+
+
 NEW_KERNELS = ("gwgrad_kernel", "gwgrad_reduce_kernel", "gbias_partial_kernel", "ggates_kernel", "gconv_kernel")
 
 

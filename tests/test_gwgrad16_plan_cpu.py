@@ -9,7 +9,14 @@ staging of every unit with the kernel's own item functions and walks every read 
 staging wrote for that unit, and holding the correlation's own element or a zero (A: zeros past
 the band, the row's end and the channels).  The units of all slices hit every (image, small
 row, band) once; each tiling's LDS is within 160 KB; the workspace is a pure function of the
-shape and the C ABI's query returns the plan's."""
+shape and the C ABI's query returns the plan's.
+
+The same program's "f32" mode plans with gw_plan (csrc/nlspn_gwgrad_plan.h, the f32 launcher's
+function) and sweeps the four f32 tilings over the same widths, (B, Hs) and cropped sizes: bands,
+slices, tiles and workspace floats.  Its plan of every weight-gradient case of
+tests/_gconv_bwd_cases.py equals the Python mirror there field by field, 4 floats is the C ABI's
+query, and the bias slices of the split-bf16 plan are the f32 plan's (the two entries' bias
+gradients are bit-equal because they run the same launches on the same slices)."""
 import json
 import os
 import shutil
@@ -17,6 +24,7 @@ import subprocess
 
 import pytest
 
+import _gconv_bwd_cases as bc
 from nlspn_eccv20_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -108,3 +116,32 @@ def test_the_check_sees_a_bad_band_or_pitch(exe, shape, bw, shift, what):
     assert _one(exe, *shape)["violations"] == []
     bad = _one(exe, *shape, bw, shift)["violations"]
     assert bad and any(what in v["detail"] for v in bad), bad
+
+
+# ---------------------------------------------------------------------------- the f32 plan
+def test_f32_plan_bands_slices_and_floats_over_the_sweep(exe):
+    r = _one(exe, "f32")
+    assert r["violations"] == 0 and r["first"] == [], r["first"]
+    # stride 1: Ws 1..400 x two (B, Hs); stride 2 (three tilings): the same plus the two crops
+    assert r["grids"] == 400 * 2 + 3 * (400 * 2 + 400 + 397)
+    assert (r["band_max"], r["target_wgs"], r["bias_slices_max"]) == (bc.GW_BW, bc.GW_TARGET, bc.GW_MAX_BIAS)
+
+
+@pytest.mark.parametrize("cid", [c["id"] for c in bc.GW_CASES])
+def test_f32_plan_is_the_mirrors_and_the_workspace_query(exe, cid):
+    c = bc.GW_BY_ID[cid]
+    shape = (c["stride"], c["Cs"], c["c0"] + c["c1"], c["B"], c["Hs"], c["Ws"], c["Hl"], c["Wl"])
+    a, m = _one(exe, "f32", *shape), bc.gw_plan(*shape)
+    assert a == _one(exe, "f32", *shape)
+    assert "".join(str(a[k]) for k in ("S", "wm", "wgm", "wgn")) == m["tiling"]
+    for k in ("mtiles", "ntiles", "nbands", "bw", "units", "ups", "nsl", "nsb", "floats"):
+        assert a[k] == m[k], (k, a, m)
+    assert (a["mt"], a["nt"], a["nthr"]) == (16 * a["wm"] * a["wgm"], 16 * a["wgn"], 64 * a["wgm"] * a["wgn"])
+    assert a["slab"] == a["mtiles"] * a["mt"] * a["ntiles"] * a["nt"] * 9 and a["bias_off"] == a["slab"] * a["nsl"]
+    assert a["floats"] == a["slab"] * a["nsl"] + a["nsb"] * max(shape[1], shape[2])
+    assert _lib.get().nlspn_gconv_wgrad_workspace_bytes(*shape) == 4 * a["floats"]
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_bf16_plan_takes_the_f32_plans_bias_slices(exe, shape):
+    assert _one(exe, *shape)["nsb"] == _one(exe, "f32", *shape)["nsb"]

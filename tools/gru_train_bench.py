@@ -53,7 +53,7 @@ def build(a, dev):
 
 def wgrad_layers(a):
     """{grid threads: (layers, FLOPs per call)} of the weight-gradient launches (the planner of
-    nlspn_gconv_host.hip gw_plan: tiling by channel counts, K slices for ~512 workgroups)."""
+    nlspn_gwgrad_plan.h gw_plan: tiling by channel counts, K slices for ~512 workgroups)."""
     half = lambda n: (n - 1) // 2 + 1  # noqa: E731
     H2, W2, H4, W4, H8, W8 = half(a.H), half(a.W), half(half(a.H)), half(half(a.W)), (a.H + 7) // 8, (a.W + 7) // 8
     hc, K = a.hidden, 8
