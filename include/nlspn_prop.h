@@ -489,7 +489,7 @@ int nlspn_gconv_affnorm(const float *x0, int c0, const float *wpk, const float *
  * nlspn_gconv_wgrad_bf16x3 (opt-in; csrc/nlspn_gwgrad16.h): the same call, arguments and
  * validation with the products on the bf16 matrix cores.  Each f32 operand a is split while
  * staging into hi = bf16(a), lo = bf16(a - hi) (round to nearest even) and the kernel sums
- * s_hi l_hi + s_hi l_lo + s_lo l_hi in f32: a term is off by at most 3 * 2^-18 |s l|.  Slabs,
+ * s_hi l_hi + s_hi l_lo + s_lo l_hi in f32: a term is off by at most 2^-15 |s l|.  Slabs,
  * slab reduce, scale and db are the f32 entry's (db is bit-equal); its workspace query is
  * nlspn_gconv_wgrad_bf16x3_workspace_bytes.  Nothing is clamped (an inf operand gives NaN).
  * Shapes with both channel counts <= 16 are forwarded to nlspn_gconv_wgrad, bit for bit.
@@ -572,6 +572,55 @@ int nlspn_gconv16(int layer, const void *x0, int c0, const void *x1, int c1, con
                   void *y16, float *y32, const float *h, float *zb, void *rh16, float *qxb, float *hout32,
                   void *hout16, int B, int Hi, int Wi, int cout, int ohs, int ows, int act, float in_div, int hc,
                   void *stream);
+
+/*
+ * GRU-mode convolutions on the bf16 matrix cores with split operands, inference only, opt-in
+ * (csrc/nlspn_gconv_x3.h; NLSPNModel.gru_precision = "bf16x3").  The same layers as nlspn_gconv
+ * on v_mfma_f32_16x16x32_bf16.  Numerics contract:
+ *   - every MFMA operand value a (f32) is the pair hi = rne_bf16(a), lo = rne_bf16(a - hi), the
+ *     subtraction in f32; weights are split once, when packed; activations once, from the f32
+ *     value the producing layer's epilogue holds;
+ *   - per output element the kernel accumulates sum (w_hi x_hi + w_hi x_lo + w_lo x_hi) in the
+ *     MFMAs' f32 accumulators (the third product on v_mfma_f32_16x16x16_bf16); lo lo is dropped;
+ *     bf16 x bf16 products are exact in f32;
+ *   - |a - hi| <= 2^-8 |a| and |a - hi - lo| <= 2^-17 |a|: a term is off by at most
+ *     (2^-17 + 2^-17 + 2^-16) |w x| = 2^-15 |w x| before accumulation rounding;
+ *   - every epilogue (bias, ReLU, tanhf, sigmoid, the GRU blend) runs in f32 on the accumulators
+ *     with nlspn_gconv's device functions; the ConvGRU state h is carried in f32 beside its
+ *     split copy; z and qx stay f32; r*h is formed in f32 and stored split;
+ *   - the 1 / 9 -> 16 first encoder layers keep the VALU kernel's f32 arithmetic (their output
+ *     is the f32 kernel's value, split); the last decoder layer stays nlspn_gconv_affnorm on the
+ *     f32 NCHW output of the layer before it;
+ *   - nothing is clamped: non-finite inputs give non-finite outputs, not necessarily of the f32
+ *     kernel's kind (inf has lo = NaN); no atomics and no waiting between workgroups: the same
+ *     bits on every run.
+ * Activation layout "c8x2": a (B, C, H, W) tensor as [B][ceil(C/8)][2][H][W][8] bf16, pad
+ * channels zero: per 8-channel block the hi cells' plane, then the lo cells'.  Weights: per co
+ * tile [cell block][tap][co][8] bf16 with cell block 2 (ci/8) + part (transposed: per output
+ * phase, the phases one after another), input channels padded to *cin_chunk (16)
+ * (nlspn_gconv_x3_pack_layout; gru.py pack_conv_x3 / pack_convt_x3); bias f32, padded to the
+ * co tiles.
+ *
+ * nlspn_gconv_x3(layer, ...): nlspn_gconv16's arguments, the half pointers (x0, x1, ys, rhs,
+ * houts) pointing to c8x2 tensors (NLSPN_GCX3_S2_SMALL: x0 f32 NCHW, wpk the module's own f32
+ * (16, cin, 3, 3) tensor).  The kinds NLSPN_GCX3_* read and write what their NLSPN_GC16_*
+ * namesakes do, and the same calls are refused with NLSPN_EINVAL before any device call: null
+ * required pointers, a preset that is not NLSPN_GCX3_*, both outputs null, an output the kind
+ * does not write, in_div != 1 outside NLSPN_GCX3_S2_SMALL, c0 not a multiple of the 16-channel
+ * chunk with two sources (the straddle case), hc not a multiple of the co tile;
+ * NLSPN_EUNSUPPORTED for a grid no tile fits.
+ */
+#define NLSPN_GCX3_S2 64
+#define NLSPN_GCX3_GRU1 65
+#define NLSPN_GCX3_GRU2 66
+#define NLSPN_GCX3_T2 67
+#define NLSPN_GCX3_T2_C16 68
+#define NLSPN_GCX3_S2_SMALL 69
+int nlspn_gconv_x3_pack_layout(int layer, int *co_tile, int *cin_chunk, int *transposed);
+int nlspn_gconv_x3(int layer, const void *x0, int c0, const void *x1, int c1, const void *wpk, const float *bias,
+                   void *ys, float *y32, const float *h, float *zb, void *rhs, float *qxb, float *hout32,
+                   void *houts, int B, int Hi, int Wi, int cout, int ohs, int ows, int act, float in_div, int hc,
+                   void *stream);
 
 #ifdef __cplusplus
 }

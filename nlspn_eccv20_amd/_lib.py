@@ -94,6 +94,9 @@ SIGNATURES = {
     "nlspn_gconv16_pack_layout": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "nlspn_gconv16": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i,
                            _i, ctypes.c_float, _i, _vp]),
+    "nlspn_gconv_x3_pack_layout": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "nlspn_gconv_x3": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i,
+                            _i, ctypes.c_float, _i, _vp]),
 }
 
 # Entry points an A/B build (NLSPN_LIB_PATH) of an earlier round may lack; any other
@@ -102,6 +105,7 @@ AB_OPTIONAL = frozenset({"nlspn_resident_status", "nlspn_resident_config", "nlsp
                          "nlspn_gconv_pack_layout", "nlspn_gconv", "nlspn_gconv_affnorm", "nlspn_gconv_dgrad", "nlspn_gconv_wgrad_workspace_bytes",
                          "nlspn_gconv_wgrad", "nlspn_gconv_gru_train", "nlspn_gconv_gru_gates_backward",
                          "nlspn_gconv16_pack_layout", "nlspn_gconv16",
+                         "nlspn_gconv_x3_pack_layout", "nlspn_gconv_x3",
                          "nlspn_gconv_wgrad_bf16x3_workspace_bytes", "nlspn_gconv_wgrad_bf16x3"})
 
 _lib = None

@@ -5,6 +5,7 @@
 #include "nlspn_host.h"
 #include "nlspn_gconv_bwd.h"
 #include "nlspn_gconv16.h"
+#include "nlspn_gconv_x3.h"
 #include "nlspn_gwgrad16.h"
 
 namespace nlspn {
@@ -20,6 +21,10 @@ NLSPN_GW_CONFIGS(NLSPN_GW_EXTERN)
 #define NLSPN_GC16_EXTERN(id, ...) extern template __global__ void gconv16_kernel<__VA_ARGS__>(Gconv16Args);
 NLSPN_GC16_CONFIGS(NLSPN_GC16_EXTERN)
 extern template __global__ void gsmall16_kernel<16>(Gconv16Args, const float *);
+// defined in nlspn_kern_gconv_x3.hip
+#define NLSPN_GCX3_EXTERN(id, ...) extern template __global__ void gconvx3_kernel<__VA_ARGS__>(GconvX3Args);
+NLSPN_GCX3_CONFIGS(NLSPN_GCX3_EXTERN)
+extern template __global__ void gsmallx3_kernel<16>(GconvX3Args, const float *);
 // defined in nlspn_kern_gwgrad16.hip
 #define NLSPN_GW16_EXTERN(...) extern template __global__ void gwgrad16_kernel<__VA_ARGS__>(GwgradArgs);
 NLSPN_GW16_CONFIGS(NLSPN_GW16_EXTERN)
@@ -28,8 +33,9 @@ NLSPN_GW16_CONFIGS(NLSPN_GW16_EXTERN)
 using namespace nlspn;
 
 namespace {
-// A preset of either family.  cc: the input channels of a chunk as packed (f32: kGcCP, which
-// every chunk size divides; f16: the chunk's CCB blocks of 8).
+// A preset of any family.  cc: the input channels of a chunk as packed (f32: kGcCP, which
+// every chunk size divides; f16: the chunk's CCB blocks of 8; split bf16: its CCB / 2 blocks of 8,
+// each a hi and a lo cell block).
 struct GcPreset {
     const void *fn;
     int mode, wgco, npx, xr, xp, cc, lds, epi;
@@ -45,6 +51,12 @@ GcPreset gc16_preset() {
     using Cfg = Gc16Cfg<MODE, WM, WN, WGM, WGN, XR, XP, CCB, EPI>;
     return GcPreset{reinterpret_cast<const void *>(&gconv16_kernel<MODE, WM, WN, WGM, WGN, XR, XP, CCB, EPI>), MODE,
                     Cfg::WGCO, Cfg::NPX, XR, XP, 8 * CCB, Cfg::LDS_BYTES, EPI};
+}
+template <int MODE, int WM, int WN, int WGM, int WGN, int XR, int XP, int CCB, int EPI>
+GcPreset gcx3_preset() {
+    using Cfg = GcX3Cfg<MODE, WM, WN, WGM, WGN, XR, XP, CCB, EPI>;
+    return GcPreset{reinterpret_cast<const void *>(&gconvx3_kernel<MODE, WM, WN, WGM, WGN, XR, XP, CCB, EPI>), MODE,
+                    Cfg::WGCO, Cfg::NPX, XR, XP, gcx3_chunk_channels(CCB), Cfg::LDS_BYTES, EPI};
 }
 bool gc_get(int layer, GcPreset &p) {
     switch (layer) {
@@ -63,8 +75,16 @@ bool gc16_get(int layer, GcPreset &p) {
         default: return false;
     }
 }
+bool gcx3_get(int layer, GcPreset &p) {
+    switch (layer) {
+#define NLSPN_GCX3_CASE(id, ...) \
+    case id: p = gcx3_preset<__VA_ARGS__>(); return true;
+        NLSPN_GCX3_CONFIGS(NLSPN_GCX3_CASE)
+        default: return false;
+    }
+}
 
-// ---- the steps the f32 forward, the data gradient and the f16 forward share
+// ---- the steps the f32 forward, the data gradient and the f16 / split-bf16 forwards share
 // the packing of a preset's weights (p null: the VALU kernel reads the module's own layout)
 int gc_pack_layout(const GcPreset *p, int *co_tile, int *cin_chunk, int *transposed) {
     if (co_tile) *co_tile = p ? p->wgco : 0;
@@ -513,6 +533,77 @@ int nlspn_gconv16(int layer, const void *x0, int c0, const void *x1, int c1, con
     if (nwg > 0x7fffffffLL || (long long)std::max(a.nb0, a.nb1) * Hi * Wi * 16 > 0x7fffffffLL)
         return fail(NLSPN_EINVAL, "gconv16: problem too large");
     return gc_launch(p, a, nwg, stream, "nlspn_gconv16");
+}
+
+// ---------------------------------------------------------------- split bf16 operands (nlspn_gconv_x3.h)
+int nlspn_gconv_x3_pack_layout(int layer, int *co_tile, int *cin_chunk, int *transposed) {
+    GcPreset p;
+    const bool small = layer == NLSPN_GCX3_S2_SMALL;  // (the module's own f32 weight layout)
+    if (!small && !gcx3_get(layer, p))
+        return fail(NLSPN_EINVAL, "gconv_x3: preset %d is not a split-bf16 preset (NLSPN_GCX3_*)", layer);
+    return gc_pack_layout(small ? nullptr : &p, co_tile, cin_chunk, transposed);
+}
+
+int nlspn_gconv_x3(int layer, const void *x0, int c0, const void *x1, int c1, const void *wpk, const float *bias,
+                   void *ys, float *y32, const float *h, float *zb, void *rhs, float *qxb, float *hout32,
+                   void *houts, int B, int Hi, int Wi, int cout, int ohs, int ows, int act, float in_div, int hc,
+                   void *stream) {
+    GcPreset p{};
+    const bool small = layer == NLSPN_GCX3_S2_SMALL;
+    if (!small && !gcx3_get(layer, p))
+        return fail(NLSPN_EINVAL, "gconv_x3: preset %d is not a split-bf16 preset (NLSPN_GCX3_*)", layer);
+    if (B < 1 || Hi < 1 || Wi < 1 || cout < 1 || c0 < 1 || c1 < 0 || (c1 > 0 && !x1))
+        return fail(NLSPN_EINVAL, "gconv_x3: bad shape B=%d Hi=%d Wi=%d c0=%d c1=%d cout=%d", B, Hi, Wi, c0, c1, cout);
+    if (!x0 || !wpk || !bias) return fail(NLSPN_EINVAL, "gconv_x3: null input, weights or bias");
+    if (act < NLSPN_GC_ACT_NONE || act > NLSPN_GC_ACT_TANH) return fail(NLSPN_EINVAL, "gconv_x3: activation %d", act);
+    // (a chunk of cell blocks is staged from one source, through one descriptor)
+    if (!small && c1 > 0 && c0 % p.cc != 0)
+        return fail(NLSPN_EINVAL, "gconv_x3: a channel chunk would straddle the two sources (c0 = %d, not a multiple of %d)",
+                    c0, p.cc);
+    if (!small && in_div != 1.f)
+        return fail(NLSPN_EINVAL, "gconv_x3: in_div %g needs the NLSPN_GCX3_S2_SMALL preset", (double)in_div);
+    const bool gru = !small && (p.epi == kGcEpiGru1 || p.epi == kGcEpiGru2), gru1 = !small && p.epi == kGcEpiGru1;
+    GconvX3Args a{};
+    a.x0 = x0; a.x1 = x1; a.w = wpk; a.bias = bias;
+    a.ys = static_cast<__bf16 *>(ys); a.y32 = y32;
+    a.h = h; a.zb = zb; a.rhs = static_cast<__bf16 *>(rhs); a.qxb = qxb;
+    a.hout32 = hout32; a.houts = static_cast<__bf16 *>(houts);
+    a.c0 = c0; a.c1 = c1; a.B = B; a.Hi = Hi; a.Wi = Wi; a.cout = cout; a.act = act; a.in_div = in_div; a.hc = hc;
+    gc_out_size(small ? kGcS2 : p.mode, Hi, Wi, a.Ho, a.Wo);
+    a.ohs = gru ? a.Ho : ohs;
+    a.ows = gru ? a.Wo : ows;
+    if (gru) {
+        if (ys || y32) return fail(NLSPN_EINVAL, "gconv_x3: a GRU launch writes no ys / y32 (output format not supported)");
+        if (hc < 1 || hc % p.wgco != 0 || !h || !zb || !qxb || c0 != hc ||
+            (gru1 ? (!rhs || cout != 3 * hc) : (!hout32 || !houts || cout != hc || c1 != 0)))
+            return fail(NLSPN_EINVAL, "gconv_x3: GRU launch needs hc %% %d == 0, c0 = hc, h, z / qx, r*h (GRU1, cout 3hc) or "
+                        "both h' outputs (GRU2, cout hc)", p.wgco);
+    } else {
+        if (!ys && !y32) return fail(NLSPN_EINVAL, "gconv_x3: both outputs null");
+        if (small && y32) return fail(NLSPN_EINVAL, "gconv_x3 small: the VALU kernel writes ys only (output format not supported)");
+    }
+    if (a.ohs < 1 || a.ows < 1 || a.ohs > a.Ho || a.ows > a.Wo)
+        return fail(NLSPN_EINVAL, "gconv_x3: stored size %dx%d outside the output %dx%d", a.ohs, a.ows, a.Ho, a.Wo);
+    if (small) {
+        if (c1 != 0 || cout != 16 || c0 * 16 * 9 > kGsMaxW)
+            return fail(NLSPN_EINVAL, "gconv_x3 small: cin %d (c1 %d), cout %d outside the VALU kernel's range (cout 16, "
+                        "cin <= 16)", c0, c1, cout);
+        const float *wf = static_cast<const float *>(wpk);
+        void *args[] = {&a, &wf};
+        return launch_kernel(reinterpret_cast<const void *>(&gsmallx3_kernel<16>), dim3(gs_grid((long long)B * a.ohs * a.ows)),
+                             dim3(kGsNT), args, 0, as_stream(stream), "nlspn_gconv_x3 small");
+    }
+    const int ccb = p.cc / 4;  // the cell blocks of a chunk: a hi and a lo one per 8 channels
+    a.nb0 = 2 * ((c0 + 7) / 8);
+    a.nb1 = 2 * ((c1 + 7) / 8);
+    a.nbp = (a.nb0 + a.nb1 + ccb - 1) / ccb * ccb;
+    a.co_tiles = (cout + p.wgco - 1) / p.wgco;
+    NLSPN_TRY(gc_tile(p, a, "gconv_x3"));
+    const long long nwg = gc_wgs(p, a);
+    // (one image's cell blocks of a source within a 32-bit buffer descriptor)
+    if (nwg > 0x7fffffffLL || (long long)std::max(a.nb0, a.nb1) * Hi * Wi * 16 > 0x7fffffffLL)
+        return fail(NLSPN_EINVAL, "gconv_x3: problem too large");
+    return gc_launch(p, a, nwg, stream, "nlspn_gconv_x3");
 }
 
 }  // extern "C"

@@ -81,6 +81,36 @@ NLSPN_HD constexpr int gc16_lds_bytes(int mode, int wgco, int xr, int xp, int cc
     return 2 * (gc16_wst(mode, wgco, ccb) + gc16_xst(xr, xp, ccb)) * 16;
 }
 
+// The split-bf16 family (nlspn_gconv_x3.h, presets NLSPN_GCX3_* of include/nlspn_prop.h), one
+// preset per kind of the f16 family with its tiling: X(id, MODE, WM, WN, WGM, WGN, XR, XP, CCB, EPI).
+// XP counts 16-byte cells and CCB the cell blocks of a chunk; a cell block is one part (hi or
+// lo) of eight channels, so CCB = 4 is a 16-channel chunk (hi0, lo0, hi1, lo1): one k-step of a
+// K = 32 and a K = 16 MFMA per tap.  Instantiated in nlspn_kern_gconv_x3.hip.
+#define NLSPN_GCX3_CONFIGS(X)                                      \
+    X(64, kGcS2, 2, 2, 2, 2, 12, 40, 4, kGcEpiAct)                 \
+    X(65, kGcS1, 2, 2, 2, 2, 6, 40, 4, kGcEpiGru1)                 \
+    X(66, kGcS1, 2, 2, 2, 2, 6, 40, 4, kGcEpiGru2)                 \
+    X(67, kGcT2, 2, 2, 2, 2, 6, 40, 4, kGcEpiAct)                  \
+    X(68, kGcT2, 1, 2, 1, 4, 6, 80, 4, kGcEpiAct)
+
+// The LDS bytes of a split-bf16 preset: two stages of a chunk's weights [CCB][taps][WGCO] and
+// window [CCB][XR][XP] in 16-byte cells, each region rounded up to whole LDS-DMA rounds of the
+// workgroup.  A hi and a lo cell per eight channels: a 16-channel chunk (CCB 4) has the bytes of
+// the f16 family's 32-channel chunk; a 32-channel chunk (CCB 8) would be 208 KB in the GRU
+// presets.  GcX3Cfg (nlspn_gconv_x3.h) uses these very functions.
+constexpr int kGcX3LdsBudget = 160 * 1024;
+NLSPN_HD constexpr int gcx3_chunk_channels(int ccb) { return 8 * (ccb / 2); }
+NLSPN_HD constexpr int gcx3_wst(int mode, int wgco, int ccb) { return gc16_round(ccb * (mode == kGcT2 ? 4 : 9) * wgco, kGcNT); }
+NLSPN_HD constexpr int gcx3_xst(int xr, int xp, int ccb) { return gc16_round(ccb * xr * xp, kGcNT); }
+NLSPN_HD constexpr int gcx3_lds_bytes(int mode, int wgco, int xr, int xp, int ccb) {
+    return 2 * (gcx3_wst(mode, wgco, ccb) + gcx3_xst(xr, xp, ccb)) * 16;
+}
+#define NLSPN_GCX3_BUDGET(id, MODE, WM, WN, WGM, WGN, XR, XP, CCB, EPI) \
+    static_assert(gcx3_lds_bytes(MODE, 16 * WM * WGM, XR, XP, CCB) <= kGcX3LdsBudget, "split-bf16 preset " #id ": LDS budget");
+NLSPN_GCX3_CONFIGS(NLSPN_GCX3_BUDGET)
+#undef NLSPN_GCX3_BUDGET
+static_assert(gcx3_lds_bytes(kGcS1, 64, 6, 40, 8) > kGcX3LdsBudget, "a 32-channel chunk does not fit the GRU presets");
+
 // What a configuration's template arguments fix of the tiling: a workgroup of WGM x WGN waves,
 // each WM x WN 16x16 blocks, owns WGCO output channels x NPX pixels; its LDS input window has
 // XR rows of pitch XP words.

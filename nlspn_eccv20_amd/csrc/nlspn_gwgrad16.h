@@ -5,8 +5,8 @@
 // Numerics.  The operands are the f32 NCHW tensors gwgrad_kernel reads.  While staging, each
 // value a becomes hi = rne_bf16(a) and lo = rne_bf16(a - hi) (the subtraction in f32), and per
 // output element the kernel accumulates sum (s_hi l_hi + s_hi l_lo + s_lo l_hi) in the f32
-// accumulators of v_mfma_f32_16x16x32_bf16; lo lo is dropped.  |a - hi - lo| <= 2^-18 |a| and
-// |lo| <= 2^-9 |a|, so a term is off by at most 3 * 2^-18 |s l| before accumulation rounding.
+// accumulators of v_mfma_f32_16x16x32_bf16; lo lo is dropped.  |a - hi - lo| <= 2^-17 |a| and
+// |lo| <= 2^-8 |a|, so a term is off by at most 2^-15 |s l| before accumulation rounding.
 // Nothing is clamped: non-finite inputs give non-finite outputs, not necessarily of the f32
 // kernel's kind (an inf operand has lo = inf - inf = NaN).  The slabs, the fixed-order slab
 // reduce, the scale factor and the bias gradient are the f32 entry's own code.

@@ -45,6 +45,15 @@ boundaries only).  ``encode_dep16`` / ``encode_aff16`` / ``gru16`` / ``decode_af
 variants; the f16 packs live in the f32 packs' cache entry (``pack16``), ``stats["fwd16"]``
 counts their launches.  The last decoder layer stays the f32 ``nlspn_gconv_affnorm``.
 
+``gru_precision = "bf16x3"`` runs them on the bf16 matrix cores instead, with f32-class operands
+(``nlspn_gconv_x3``, ``csrc/nlspn_gconv_x3.h``): every f32 operand is the pair ``hi = bf16(a)``,
+``lo = bf16(a - hi)`` (``split_bf16``) and the kernels accumulate ``w_hi x_hi + w_hi x_lo +
+w_lo x_hi`` in f32.  Weights are split once when packed (``pack_conv_x3`` / ``pack_convt_x3``),
+activations once in the epilogue that produces them; between the layers they travel in the
+``c8x2`` layout (``to_c8x2`` / ``from_c8x2``: tests and boundaries only).  ``encode_dep_x3`` /
+``encode_aff_x3`` / ``gru_x3`` / ``decode_aff_x3`` mirror the f16 methods, the packs live in the
+same cache entry (``pack_x3``) and ``stats["fwd_x3"]`` counts the launches.
+
 Opt-in under gradients (``GruConvs.wgrad_precision = "bf16x3"``, set through
 ``NLSPNModel.gru_wgrad_precision``) the weight gradients run on the bf16 matrix cores with each
 f32 operand split into two bf16 parts (``nlspn_gconv_wgrad_bf16x3``, ``csrc/nlspn_gwgrad16.h``);
@@ -62,13 +71,16 @@ import torch.nn as nn
 from . import _lib
 
 __all__ = ["GruConvs", "pack_adjoint", "pack_adjoint_s1", "unpack_conv", "unpack_convt", "to_c8", "from_c8",
-           "pack_conv16", "pack_convt16", "unpack_conv16", "unpack_convt16", "GC_S2", "GC_S2_C16", "GC_GRU1", "GC_GRU2", "GC_T2", "GC_T2_C16", "GC_S2_SMALL"]
+           "pack_conv16", "pack_convt16", "unpack_conv16", "unpack_convt16", "split_bf16", "to_c8x2", "from_c8x2",
+           "pack_conv_x3", "pack_convt_x3", "unpack_conv_x3", "unpack_convt_x3", "GC_S2", "GC_S2_C16", "GC_GRU1", "GC_GRU2", "GC_T2", "GC_T2_C16", "GC_S2_SMALL"]
 
 GC_S2, GC_S2_C16, GC_GRU1, GC_GRU2, GC_T2, GC_T2_C16, GC_S2_SMALL = range(7)
 # the data-gradient presets (NLSPN_GC_DG_*): the adjoint kind's tiling, derivative epilogue
 GC_DG_T2, GC_DG_T2_C16, GC_DG_S2, GC_DG_S2_C16, GC_DG_S1 = range(32, 37)
 # the f16-operand presets (NLSPN_GC16_*, csrc/nlspn_gconv16.h)
 GC16_S2, GC16_GRU1, GC16_GRU2, GC16_T2, GC16_T2_C16, GC16_S2_SMALL = range(48, 54)
+# the split-bf16 presets (NLSPN_GCX3_*, csrc/nlspn_gconv_x3.h)
+GCX3_S2, GCX3_GRU1, GCX3_GRU2, GCX3_T2, GCX3_T2_C16, GCX3_S2_SMALL = range(64, 70)
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 # the transposed conv's taps per output phase (py, px), in the kernel's order
 # (nlspn_gconv.h gc_tap): ky = 1 (py = 0) or 0, 2 (py = 1); likewise kx
@@ -80,7 +92,9 @@ class _Family(typing.NamedTuple):
     """A preset family: the pack-layout query of the C ABI, the weight dtype and the inner
     channel block (the f32 kernels read [co_tile][cin_pad][tap][co]; the f16 ones the same with
     the input channels in blocks of 8 innermost, [co_tile][cin_pad/8][tap][co][8]), and its
-    presets by layer kind (s2_c16 / t2_c16: at most 16 output channels; small: the VALU kernel)."""
+    presets by layer kind (s2_c16 / t2_c16: at most 16 output channels; small: the VALU kernel).
+    ``split``: every f32 weight goes in as two bf16 parts, per 8 input channels a hi block then
+    a lo block ([co_tile][2 cin_pad / 8][tap][co][8]: the c8x2 layout's channel order)."""
     query: str
     dtype: torch.dtype
     block: int
@@ -91,12 +105,15 @@ class _Family(typing.NamedTuple):
     small: int
     gru1: int
     gru2: int
+    split: bool = False
 
 
 _F32 = _Family("nlspn_gconv_pack_layout", torch.float32, 1, GC_S2, GC_S2_C16, GC_T2, GC_T2_C16, GC_S2_SMALL, GC_GRU1, GC_GRU2)
 # (the f16 stride-2 conv has one tiling for every width)
 _F16 = _Family("nlspn_gconv16_pack_layout", torch.float16, 8, GC16_S2, GC16_S2, GC16_T2, GC16_T2_C16, GC16_S2_SMALL,
                GC16_GRU1, GC16_GRU2)
+_X3 = _Family("nlspn_gconv_x3_pack_layout", torch.bfloat16, 8, GCX3_S2, GCX3_S2, GCX3_T2, GCX3_T2_C16, GCX3_S2_SMALL,
+              GCX3_GRU1, GCX3_GRU2, split=True)
 _TAPS = [[(ky, kx) for ky in range(3) for kx in range(3)]]  # a conv: one part, all nine taps
 
 
@@ -106,6 +123,21 @@ def _layout_of(fam, layer):
     co, cc, tr = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     _lib.check(getattr(lib, fam.query)(layer, ctypes.byref(co), ctypes.byref(cc), ctypes.byref(tr)))
     return co.value, cc.value, bool(tr.value)
+
+
+def split_bf16(x: torch.Tensor):
+    """(hi, lo) of an f32 tensor, both bfloat16: hi = x rounded to nearest-even, lo = the f32
+    difference x - hi rounded to nearest-even.  |x - hi - lo| <= 2^-17 |x|."""
+    x = x.float()
+    hi = x.to(torch.bfloat16)
+    return hi, (x - hi.float()).to(torch.bfloat16)
+
+
+def _split_blocks(w):
+    """(N, C, T) f32, C a multiple of 8 -> (N, 2 C, T) bf16: per 8-channel block its hi part, then its lo part."""
+    N, C, T = w.shape
+    hi, lo = split_bf16(w)
+    return torch.stack([hi.reshape(N, C // 8, 8, T), lo.reshape(N, C // 8, 8, T)], 2).reshape(N, 2 * C, T)
 
 
 def _pad_bias(bias, cout, n, device):
@@ -118,11 +150,12 @@ def _pad_bias(bias, cout, n, device):
 def _pack(fam, transposed, weight, bias, layer):
     """The packed weights and padded f32 bias of a conv ((Cout, Cin, 3, 3)) or transposed conv
     ((Cin, Cout, 3, 3)) for a preset of family ``fam``: converted to the family's dtype first
-    (half: one rounding to nearest-even), then per part (a conv: one; a transposed conv: its
-    four output phases, one after another) [co_tile][cin_pad / block][tap][co][block]."""
+    (half: one rounding to nearest-even; a split family: split_bf16, the hi and lo blocks
+    interleaved), then per part (a conv: one; a transposed conv: its four output phases, one
+    after another) [co_tile][cin_pad / block][tap][co][block]."""
     wgco, cc, tr = _layout_of(fam, layer)
     assert tr == transposed
-    dtype, cb = fam.dtype, fam.block
+    dtype, cb = (torch.float32 if fam.split else fam.dtype), fam.block
     wd = weight.detach().to(dtype)
     if transposed:
         wd = wd.transpose(0, 1)
@@ -134,20 +167,26 @@ def _pack(fam, transposed, weight, bias, layer):
         w = torch.zeros((ct * wgco, cp, len(taps)), device=weight.device, dtype=dtype)
         for t, (ky, kx) in enumerate(taps):
             w[:cout, :cin, t] = wd[:, :, ky, kx]
-        parts.append(w.reshape(ct, wgco, cp // cb, cb, len(taps)).permute(0, 2, 4, 1, 3).contiguous().reshape(-1))
+        if fam.split:
+            w = _split_blocks(w)
+        parts.append(w.reshape(ct, wgco, w.shape[1] // cb, cb, len(taps)).permute(0, 2, 4, 1, 3).contiguous().reshape(-1))
     return torch.cat(parts), _pad_bias(bias, cout, ct * wgco, weight.device)
 
 
 def _unpack(fam, transposed, w, cout, cin, layer):
-    """Inverse of _pack: the module's (Cout, Cin, 3, 3) or (Cin, Cout, 3, 3) tensor, in w's dtype."""
+    """Inverse of _pack: the module's (Cout, Cin, 3, 3) or (Cin, Cout, 3, 3) tensor, in w's dtype
+    (a split family: hi + lo in f32)."""
     wgco, cc, _ = _layout_of(fam, layer)
     cb = fam.block
     ct, cp = (cout + wgco - 1) // wgco, (cin + cc - 1) // cc * cc
-    out = torch.zeros((cout, cin, 3, 3), device=w.device, dtype=w.dtype)
+    cpk = 2 * cp if fam.split else cp  # the packed channels: a hi and a lo block per 8
+    out = torch.zeros((cout, cin, 3, 3), device=w.device, dtype=torch.float32 if fam.split else w.dtype)
     o = 0
     for taps in (_T_TAPS if transposed else _TAPS):
-        n = ct * cp * len(taps) * wgco
-        part = w[o:o + n].reshape(ct, cp // cb, len(taps), wgco, cb).permute(0, 3, 1, 4, 2).reshape(ct * wgco, cp, len(taps))
+        n = ct * cpk * len(taps) * wgco
+        part = w[o:o + n].reshape(ct, cpk // cb, len(taps), wgco, cb).permute(0, 3, 1, 4, 2).reshape(ct * wgco, cpk, len(taps))
+        if fam.split:
+            part = part.float().reshape(ct * wgco, cp // 8, 2, 8, len(taps)).sum(2).reshape(ct * wgco, cp, len(taps))
         for t, (ky, kx) in enumerate(taps):
             out[:, :, ky, kx] = part[:cout, :cin, t]
         o += n
@@ -159,7 +198,9 @@ def _unpack(fam, transposed, w, cout, cin, layer):
 _layout, _layout16 = functools.partial(_layout_of, _F32), functools.partial(_layout_of, _F16)
 pack_conv, pack_convt = functools.partial(_pack, _F32, False), functools.partial(_pack, _F32, True)
 pack_conv16, pack_convt16 = functools.partial(_pack, _F16, False), functools.partial(_pack, _F16, True)
+pack_conv_x3, pack_convt_x3 = functools.partial(_pack, _X3, False), functools.partial(_pack, _X3, True)
 unpack_conv, unpack_conv16 = functools.partial(_unpack, _F32, False), functools.partial(_unpack, _F16, False)
+unpack_conv_x3 = functools.partial(_unpack, _X3, False)
 
 
 def unpack_convt(w, cin, cout, layer):
@@ -168,6 +209,10 @@ def unpack_convt(w, cin, cout, layer):
 
 def unpack_convt16(w, cin, cout, layer):
     return _unpack(_F16, True, w, cout, cin, layer)
+
+
+def unpack_convt_x3(w, cin, cout, layer):
+    return _unpack(_X3, True, w, cout, cin, layer)
 
 
 def _conv_of(seq):
@@ -251,6 +296,44 @@ def from_c8(y: torch.Tensor, C: int) -> torch.Tensor:
     """Inverse of to_c8: the (B, C, H, W) half tensor of a c8 tensor."""
     B, nb, H, W, _ = y.shape
     return y.permute(0, 1, 4, 2, 3).reshape(B, nb * 8, H, W)[:, :C].contiguous()
+
+
+# ---------------------------------------------------------------------- split bf16 operands (nlspn_gconv_x3.h)
+def to_c8x2(x: torch.Tensor) -> torch.Tensor:
+    """(B, C, H, W) f32 -> the kernels' c8x2 layout, one (B, ceil(C/8), 2, H, W, 8) bfloat16 tensor:
+    per 8-channel block the hi part's cells, then the lo part's (split_bf16), pad channels zero.
+    For tests and boundaries, never on the hot path."""
+    B, C, H, W = x.shape
+    nb = (C + 7) // 8
+    y = torch.zeros((B, nb * 8, H, W), device=x.device, dtype=torch.float32)
+    y[:, :C] = x.float()
+    return torch.stack([p.reshape(B, nb, 8, H, W).permute(0, 1, 3, 4, 2) for p in split_bf16(y)], 2).contiguous()
+
+
+def from_c8x2(y: torch.Tensor, C: int, parts: bool = False):
+    """Inverse of to_c8x2: the (B, C, H, W) f32 sum hi + lo of a c8x2 tensor (exact: the sum of two
+    bf16 values of a split fits f32); with ``parts`` the (hi, lo) pair of bfloat16 tensors instead."""
+    B, nb, _, H, W, _ = y.shape
+    hi, lo = (y[:, :, s].permute(0, 1, 4, 2, 3).reshape(B, nb * 8, H, W)[:, :C].contiguous() for s in (0, 1))
+    return (hi, lo) if parts else hi.float() + lo.float()
+
+
+class _Mode(typing.NamedTuple):
+    """An inference precision of the matrix-core families: its _Family (weight / activation dtype,
+    split or not), C entry, pack-cache key and stats counter."""
+    fam: _Family
+    entry: str
+    key: str
+    stat: str
+
+    def empty(self, B, C, H, W, device):
+        """An uninitialised activation of C channels in the family's layout (c8 / c8x2)."""
+        shape = (B, (C + 7) // 8, 2, H, W, 8) if self.fam.split else (B, (C + 7) // 8, H, W, 8)
+        return torch.empty(shape, device=device, dtype=self.fam.dtype)
+
+
+_M16 = _Mode(_F16, "nlspn_gconv16", "f16", "fwd16")
+_MX3 = _Mode(_X3, "nlspn_gconv_x3", "x3", "fwd_x3")
 
 
 class _ChainFn(torch.autograd.Function):
@@ -353,8 +436,9 @@ class GruConvs:
         ``wgrad`` (kernel launches of the weight / bias gradients) and ``gates_bwd``; ``gru_fwd``
         counts ConvGRU cell forwards; ``fwd16`` the forward launches of the f16-operand family;
         ``wgrad_x3`` the weight / bias gradient launches of the ``"bf16x3"`` mode, counted as
-        ``wgrad`` counts the f32 entry's."""
-        self.stats = {"fwd": 0, "dgrad": 0, "wgrad": 0, "gates_bwd": 0, "gru_fwd": 0, "fwd16": 0, "wgrad_x3": 0}
+        ``wgrad`` counts the f32 entry's; ``fwd_x3`` the forward launches of the split-bf16 family."""
+        self.stats = {"fwd": 0, "dgrad": 0, "wgrad": 0, "gates_bwd": 0, "gru_fwd": 0, "fwd16": 0, "wgrad_x3": 0,
+                      "fwd_x3": 0}
 
     @staticmethod
     def supported(model) -> bool:
@@ -414,85 +498,116 @@ class GruConvs:
     def pack16(self, model):
         """The f16 packs (pack_conv16 / pack_convt16) beside the f32 ones, in the same cache entry
         under the same invalidation key, packed when first needed."""
+        return self._pack_mode(_M16, model, "fp16")
+
+    def pack_x3(self, model):
+        """The split-bf16 packs (pack_conv_x3 / pack_convt_x3), cached as pack16's are."""
+        return self._pack_mode(_MX3, model, "bf16x3")
+
+    def _pack_mode(self, M, model, name):
         P = self.pack(model)
-        if "f16" in P:
+        if M.key in P:
             return P
-        # (the f16 chains start on the VALU kernel, which reads f32 NCHW, and end on the f32 last
-        # decoder layer: the reference's architecture; anything else has no f16 kernel)
+        # (the chains start on the VALU kernel, which reads f32 NCHW, and end on the f32 last
+        # decoder layer: the reference's architecture; anything else has no such kernel)
         first = [_conv_of(seq[0]) for seq in (model.encode_dep, model.encode_aff)]
         if any(c.out_channels != 16 or c.in_channels > 16 for c in first) or len(model.decode_aff) < 2:
-            raise NotImplementedError("gru_precision = 'fp16' needs the reference's GRU-mode layers (1 / 9 -> 16 first "
+            raise NotImplementedError(f"gru_precision = '{name}' needs the reference's GRU-mode layers (1 / 9 -> 16 first "
                                       "encoder convs, at least two decoder layers)")
         with torch.no_grad():
-            gru1, gru2 = _gru_layers(_F16, model.GRU)
-            P["f16"] = {"dep": _chain_layers(_F16, list(model.encode_dep)),
-                        "aff": _chain_layers(_F16, list(model.encode_aff)[:3], ACT_TANH),
-                        "dec": _chain_layers(_F16, list(model.decode_aff)[:-1]), "gru1": gru1, "gru2": gru2}
+            gru1, gru2 = _gru_layers(M.fam, model.GRU)
+            P[M.key] = {"dep": _chain_layers(M.fam, list(model.encode_dep)),
+                        "aff": _chain_layers(M.fam, list(model.encode_aff)[:3], ACT_TANH),
+                        "dec": _chain_layers(M.fam, list(model.decode_aff)[:-1]), "gru1": gru1, "gru2": gru2}
         return P
 
-    # ------------------------------------------------------------------ f16 launches (inference)
-    def _run16(self, L, x0, c0, B, Hi, Wi, x1=None, c1=0, y16=None, y32=None, ohs=0, ows=0, in_div=1.0, h=None, zb=None,
-               rh16=None, qxb=None, hout32=None, hout16=None, hc=0):
-        _lib.call("nlspn_gconv16", x0.device, L.layer, x0, c0, x1, c1, L.w, L.b, y16, y32, h, zb, rh16, qxb, hout32,
-                  hout16, B, Hi, Wi, L.cout, ohs, ows, L.act, in_div, hc, _lib.STREAM)
-        self.stats["fwd16"] += 1
+    # ------------------------------------------------------------------ f16 / split-bf16 launches (inference)
+    # M: the mode (_M16 / _MX3); "c8" below stands for the mode's activation layout (c8 / c8x2)
+    def _runm(self, M, L, x0, c0, B, Hi, Wi, x1=None, c1=0, yh=None, y32=None, ohs=0, ows=0, in_div=1.0, h=None, zb=None,
+              rhh=None, qxb=None, hout32=None, houth=None, hc=0):
+        _lib.call(M.entry, x0.device, L.layer, x0, c0, x1, c1, L.w, L.b, yh, y32, h, zb, rhh, qxb, hout32,
+                  houth, B, Hi, Wi, L.cout, ohs, ows, L.act, in_div, hc, _lib.STREAM)
+        self.stats[M.stat] += 1
 
-    def _enc16(self, layers, x, in_div, both):
+    def _encm(self, M, layers, x, in_div, both):
         """A stride-2 encoder chain: f32 NCHW in, c8 between the layers and out (both: the last
         layer also writes f32 NCHW: (y32, y16))."""
         B, _, Hi, Wi = x.shape
         y32 = None
         for i, L in enumerate(layers):
             Ho, Wo = (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1
-            y = torch.empty((B, (L.cout + 7) // 8, Ho, Wo, 8), device=x.device, dtype=torch.float16)
+            y = M.empty(B, L.cout, Ho, Wo, x.device)
             if both and i == len(layers) - 1:
                 y32 = torch.empty((B, L.cout, Ho, Wo), device=x.device, dtype=torch.float32)
-            self._run16(L, x, L.cin, B, Hi, Wi, y16=y, y32=y32, ohs=Ho, ows=Wo, in_div=in_div if i == 0 else 1.0)
+            self._runm(M, L, x, L.cin, B, Hi, Wi, yh=y, y32=y32, ohs=Ho, ows=Wo, in_div=in_div if i == 0 else 1.0)
             x, Hi, Wi = y, Ho, Wo
         return (y32, x) if both else x
 
-    def encode_dep16(self, P, new_pred, max_depth):
-        """encode_dep(new_pred / max_depth) on the f16 matrix cores: the c8 features."""
-        return self._enc16(P["f16"]["dep"], new_pred.contiguous().float(), float(max_depth), False)
-
-    def encode_aff16(self, P, aff):
-        """encode_aff on the f16 matrix cores: the initial state (h f32, its c8 copy)."""
-        return self._enc16(P["f16"]["aff"], aff.contiguous().float(), 1.0, True)
-
-    def gru16(self, P, state, x16):
-        """ConvGRU on the f16 matrix cores: state = (h f32, h c8), x16 the c8 input; the new state."""
+    def _grum(self, M, P, state, xh):
         self.stats["gru_fwd"] += 1
-        h, h16 = state
+        h, hh = state
         hc = P["hc"]
         B, _, H, W = h.shape
         z, qx, hn = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h)
-        rh16, hn16 = torch.empty_like(h16), torch.empty_like(h16)
-        F = P["f16"]
-        self._run16(F["gru1"], h16, hc, B, H, W, x1=x16, c1=hc, h=h, zb=z, rh16=rh16, qxb=qx, hc=hc)
-        self._run16(F["gru2"], rh16, hc, B, H, W, h=h, zb=z, qxb=qx, hout32=hn, hout16=hn16, hc=hc)
-        return hn, hn16
+        rhh, hnh = torch.empty_like(hh), torch.empty_like(hh)
+        F = P[M.key]
+        self._runm(M, F["gru1"], hh, hc, B, H, W, x1=xh, c1=hc, h=h, zb=z, rhh=rhh, qxb=qx, hc=hc)
+        self._runm(M, F["gru2"], rhh, hc, B, H, W, h=h, zb=z, qxb=qx, hout32=hn, houth=hnh, hc=hc)
+        return hn, hnh
 
-    def decode_aff16(self, P, state, crop, gamma=None, kind=None):
-        """decode_aff on the f16 matrix cores up to its last layer's f32 NCHW input; the last
-        layer (16 -> K, the crop and the fused normalisation) is the f32 family's, unchanged."""
+    def _decm(self, M, P, state, crop, gamma, kind):
         x = state[1]
-        B, _, Hi, Wi, _ = x.shape
-        layers = P["f16"]["dec"]
+        B, Hi, Wi = x.shape[0], x.shape[-3], x.shape[-2]
+        layers = P[M.key]["dec"]
         y32 = None
         for i, L in enumerate(layers):
             Ho, Wo = 2 * Hi, 2 * Wi
             last = i == len(layers) - 1
             if last:
                 y32 = torch.empty((B, L.cout, Ho, Wo), device=x.device, dtype=torch.float32)
-                self._run16(L, x, L.cin, B, Hi, Wi, y32=y32, ohs=Ho, ows=Wo)
+                self._runm(M, L, x, L.cin, B, Hi, Wi, y32=y32, ohs=Ho, ows=Wo)
             else:
-                y = torch.empty((B, (L.cout + 7) // 8, Ho, Wo, 8), device=x.device, dtype=torch.float16)
-                self._run16(L, x, L.cin, B, Hi, Wi, y16=y, ohs=Ho, ows=Wo)
+                y = M.empty(B, L.cout, Ho, Wo, x.device)
+                self._runm(M, L, x, L.cin, B, Hi, Wi, yh=y, ohs=Ho, ows=Wo)
                 x = y
             Hi, Wi = Ho, Wo
         Pl = dict(P)
         Pl["dec"] = P["dec"][-1:]
         return self.decode_aff(Pl, y32, crop, gamma=gamma, kind=kind)
+
+    def encode_dep16(self, P, new_pred, max_depth):
+        """encode_dep(new_pred / max_depth) on the f16 matrix cores: the c8 features."""
+        return self._encm(_M16, P["f16"]["dep"], new_pred.contiguous().float(), float(max_depth), False)
+
+    def encode_aff16(self, P, aff):
+        """encode_aff on the f16 matrix cores: the initial state (h f32, its c8 copy)."""
+        return self._encm(_M16, P["f16"]["aff"], aff.contiguous().float(), 1.0, True)
+
+    def gru16(self, P, state, x16):
+        """ConvGRU on the f16 matrix cores: state = (h f32, h c8), x16 the c8 input; the new state."""
+        return self._grum(_M16, P, state, x16)
+
+    def decode_aff16(self, P, state, crop, gamma=None, kind=None):
+        """decode_aff on the f16 matrix cores up to its last layer's f32 NCHW input; the last
+        layer (16 -> K, the crop and the fused normalisation) is the f32 family's, unchanged."""
+        return self._decm(_M16, P, state, crop, gamma, kind)
+
+    def encode_dep_x3(self, P, new_pred, max_depth):
+        """encode_dep(new_pred / max_depth) on the bf16 matrix cores, split operands: the c8x2 features."""
+        return self._encm(_MX3, P["x3"]["dep"], new_pred.contiguous().float(), float(max_depth), False)
+
+    def encode_aff_x3(self, P, aff):
+        """encode_aff, split operands: the initial state (h f32, its c8x2 copy)."""
+        return self._encm(_MX3, P["x3"]["aff"], aff.contiguous().float(), 1.0, True)
+
+    def gru_x3(self, P, state, xs):
+        """ConvGRU, split operands: state = (h f32, h c8x2), xs the c8x2 input; the new state."""
+        return self._grum(_MX3, P, state, xs)
+
+    def decode_aff_x3(self, P, state, crop, gamma=None, kind=None):
+        """decode_aff, split operands, up to its last layer's f32 NCHW input; the last layer is
+        the f32 family's, unchanged (as decode_aff16)."""
+        return self._decm(_MX3, P, state, crop, gamma, kind)
 
     # ------------------------------------------------------------------ launches
     @staticmethod

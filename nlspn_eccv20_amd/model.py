@@ -257,7 +257,9 @@ class NLSPNModel(nn.Module):
         # gru_precision = "fp16": at inference, where the HIP path runs, the same convolutions on
         # the f16 matrix cores (gru.py, nlspn_gconv16.h; f32 accumulation and epilogues, f32 state).
         # "fp32" (default) is the path above, bit for bit; ignored under gradients and with
-        # native_gru = False.  Off by default whatever the speed: the numerics differ
+        # native_gru = False.  Off by default whatever the speed: the numerics differ.
+        # gru_precision = "bf16x3": the same, on the bf16 matrix cores with every f32 operand split
+        # into two bf16 parts (nlspn_gconv_x3.h): f32-class operands, same rules
         self.gru_precision = "fp32"
         self._gru_convs = GruConvs()
         # gru_wgrad_precision = "bf16x3": where the native training path runs (native_gru_train,
@@ -274,8 +276,8 @@ class NLSPNModel(nn.Module):
 
     @gru_precision.setter
     def gru_precision(self, value):
-        if value not in ("fp32", "fp16"):
-            raise ValueError(f"gru_precision must be 'fp32' or 'fp16', got {value!r}")
+        if value not in ("fp32", "fp16", "bf16x3"):
+            raise ValueError(f"gru_precision must be 'fp32', 'fp16' or 'bf16x3', got {value!r}")
         object.__setattr__(self, "_gru_precision", value)
 
     @property
@@ -291,6 +293,10 @@ class NLSPNModel(nn.Module):
     def _gru_fp16(self, x) -> bool:
         """The f16-operand convolutions run: asked for, gradients off, and the HIP path would run."""
         return self.gru_precision == "fp16" and not torch.is_grad_enabled() and self._native_gru(x)
+
+    def _gru_x3(self, x) -> bool:
+        """The split-bf16 convolutions run: by the rule of _gru_fp16."""
+        return self.gru_precision == "bf16x3" and not torch.is_grad_enabled() and self._native_gru(x)
 
     def gru_channels_last(self):
         """Put the GRU-mode convolutions (ConvGRU, encode_aff / encode_dep, decode_aff) in
@@ -366,10 +372,12 @@ class NLSPNModel(nn.Module):
 
     def _aff_head(self, aff_feat):
         """nlspnmodel.py:228-234 (+ the _clip_as crop :237-250)."""
-        if isinstance(aff_feat, tuple):  # the fp16 path's state (h f32, h c8), _gru_update
+        if isinstance(aff_feat, tuple):  # the fp16 / bf16x3 path's state (h f32, h c8 / c8x2), _gru_update
             gc = self._gru_convs
-            aff = gc.decode_aff16(gc.pack16(self), aff_feat, (self.args.patch_height, self.args.patch_width),
-                                  gamma=self.aff_scale_const, kind=self.args.affinity)
+            x3 = aff_feat[1].dtype == torch.bfloat16
+            dec, P = (gc.decode_aff_x3, gc.pack_x3(self)) if x3 else (gc.decode_aff16, gc.pack16(self))
+            aff = dec(P, aff_feat, (self.args.patch_height, self.args.patch_width),
+                      gamma=self.aff_scale_const, kind=self.args.affinity)
             if aff.shape[1] == self.num_neighbors + 1:
                 return aff
             return affinity_normalization(aff, self.aff_scale_const, self.args.affinity)
@@ -482,6 +490,13 @@ class NLSPNModel(nn.Module):
             if k == 2:
                 aff_feat = gc.encode_aff16(P, aff)
             return gc.gru16(P, aff_feat, dep16)
+        if self._gru_x3(new_pred):
+            gc = self._gru_convs
+            P = gc.pack_x3(self)
+            deps = gc.encode_dep_x3(P, new_pred, self.args.max_depth)
+            if k == 2:
+                aff_feat = gc.encode_aff_x3(P, aff)
+            return gc.gru_x3(P, aff_feat, deps)
         if self._native_gru(new_pred):
             gc = self._gru_convs
             P = gc.pack(self)
