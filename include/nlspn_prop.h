@@ -127,6 +127,39 @@ int nlspn_head_epilogue_prologue(int dtype, const void *fe1, const void *fd_oa, 
                                  unsigned flags, void *stream);
 
 /*
+ * The head epilogue and its fused-prologue form on the bf16 matrix cores with split
+ * operands ("bf16x3", opt-in; csrc/nlspn_heads_x3.h).  Same arguments, validation order
+ * and refusals as the entries above; wm is the bf16 array packed by
+ * nlspn_head_x3_pack_weights (nlspn_head_x3_packed_size elements), wv and bias are
+ * bit-equal to the f32 pack's.  float32 tensors only.  Numerics contract:
+ *   - every MFMA operand a (f32) travels as hi = rne_bf16(a), lo = rne_bf16(a - hi), the
+ *     subtraction in f32: weights split once when packed, fe1 / off_aff_fd1 while staged;
+ *   - per output element sum (w_hi x_hi + w_hi x_lo + w_lo x_hi) in f32 accumulators; lo lo
+ *     is dropped; a term is off by at most 2^-15 |w x|;
+ *   - the id / cf convolutions' one-channel decoder halves (id_fd1, cf_fd1) stay f32 VALU
+ *     fmaf sums of unsplit operands, in the f32 kernel's order;
+ *   - bias, ReLU, sigmoid and the fused prologue run in f32, by the f32 kernel's code;
+ *   - nothing is clamped (a NaN reaches exactly its 3x3 neighbourhood, an inf gives NaN
+ *     there); no atomics: the same bits on every run.
+ * H * W below 2^25 (a round's 16 planes are addressed with 32-bit byte offsets).
+ */
+int nlspn_head_x3_packed_size(int C, int nout, int64_t *wm_bf16_elems, int64_t *wv_floats,
+                              int64_t *bias_floats);
+int nlspn_head_x3_pack_weights(const float *w_oa, const float *b_oa, const float *w_id,
+                               const float *b_id, const float *w_cf, const float *b_cf,
+                               void *wm, float *wv, float *bias, int C, int nout, void *stream);
+int nlspn_head_epilogue_x3(int dtype, const void *fe1, const void *fd_oa, const void *fd_id,
+                           const void *fd_cf, const void *wm, const float *wv,
+                           const float *bias, void *off_aff, void *pred_init, void *conf,
+                           int B, int C, int H, int W, int nout, void *stream);
+int nlspn_head_epilogue_prologue_x3(int dtype, const void *fe1, const void *fd_oa,
+                                    const void *fd_id, const void *fd_cf, const void *wm,
+                                    const float *wv, const float *bias, const void *dep,
+                                    const float *gamma, void *pred_init, void *conf_out,
+                                    void *aff_out, void *off_out, void *p0, int B, int C, int H,
+                                    int W, int kh, int kw, int kind, unsigned flags, void *stream);
+
+/*
  * Affinity normalisation + reference-tap insertion.
  * Replaces NLSPNModel._affinity_normalization (src/model/nlspnmodel.py:179-201)
  * followed by _aff_insert (:261-269).

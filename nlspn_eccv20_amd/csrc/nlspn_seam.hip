@@ -1,15 +1,18 @@
 // C ABI of the seam-2 and head entry points (see include/nlspn_prop.h): the modulated
 // deformable convolution forward and backward, the S2D pyramid, the head epilogue and its
 // weight packing, and the affinity normalisation's forward.  The DCN, S2D, packing and
-// normalisation kernels are instantiated here; the head kernels in nlspn_kern_heads.hip.
+// normalisation kernels are instantiated here; the head kernels in nlspn_kern_heads.hip and
+// nlspn_kern_heads_x3.hip.
 #include "nlspn_host.h"
 #include "nlspn_affnorm.h"
 #include "nlspn_heads.h"
+#include "nlspn_heads_x3.h"
 #include "nlspn_mdcn.h"
 #include "nlspn_s2d.h"
 
 namespace nlspn {
 NLSPN_HD_BUILDS(NLSPN_HD_EXTERN)  // defined in nlspn_kern_heads.hip
+NLSPN_HDX3_BUILDS(NLSPN_HDX3_EXTERN)  // defined in nlspn_kern_heads_x3.hip
 }  // namespace nlspn
 
 using namespace nlspn;
@@ -115,6 +118,40 @@ int launch_heads(HeadsArgs &a, void *stream) {
     return launch_kernel(fn, dim3((unsigned)grid), dim3(kHdNT), args, (size_t)lds, as_stream(stream), "nlspn_head_epilogue");
 }
 
+// The split-bf16 builds (nlspn_heads_x3.h; workgroups per CU: its header).
+int launch_heads_x3(HeadsArgs &a, void *stream) {
+    const int C = a.C, W = a.W, nout = a.nout;
+    const long long grid = (long long)a.B * a.tiles_x * a.tiles_y;
+    // (the window's buffer loads address a round's 16 planes with 32-bit byte offsets)
+    if (grid > 0x7fffffffLL || 64LL * a.H * W > 0x7fffffffLL) return fail(NLSPN_EINVAL, "input too large");
+    const bool vec = W % 4 == 0 && aligned(a.fe1, 16) && aligned(a.fd_oa, 16) && aligned(a.fd_id, 16) &&
+                     aligned(a.fd_cf, 16);
+    const int mb = hx3_mb(nout);
+    const void *fn = nullptr;
+    switch (mb) {
+#define NLSPN_HDX3_CASE(MB)                                                       \
+    case MB:                                                                      \
+        fn = vec ? reinterpret_cast<const void *>(&headsx3_kernel<MB, true>)      \
+                 : reinterpret_cast<const void *>(&headsx3_kernel<MB, false>);    \
+        break;
+        NLSPN_HDX3_CASE(1)
+        NLSPN_HDX3_CASE(2)
+        NLSPN_HDX3_CASE(3)
+        NLSPN_HDX3_CASE(5)
+#undef NLSPN_HDX3_CASE
+        default: return fail(NLSPN_EUNSUPPORTED, "head epilogue: nout=%d", nout);
+    }
+    if (a.aff_out)  // the fused propagation prologue (nout = 24: MB = 1)
+        fn = vec ? reinterpret_cast<const void *>(&headsx3_kernel<1, true, true>)
+                 : reinterpret_cast<const void *>(&headsx3_kernel<1, false, true>);
+    const int lds = hx3_lds_bytes(mb, C);
+    if (lds > kHx3LdsBudget) return fail(NLSPN_EUNSUPPORTED, "head epilogue: C=%d needs %d bytes of LDS", C, lds);
+    if (lds > 65536) NLSPN_TRY(set_lds_attr(fn, lds));
+    void *args[] = {&a};
+    return launch_kernel(fn, dim3((unsigned)grid), dim3(kHdNT), args, (size_t)lds, as_stream(stream),
+                         "nlspn_head_epilogue_x3");
+}
+
 }  // namespace
 
 extern "C" {
@@ -198,6 +235,71 @@ int nlspn_head_epilogue_prologue(int dtype, const void *fe1, const void *fd_oa, 
                 static_cast<const float *>(dep), gamma, static_cast<float *>(aff_out), static_cast<float *>(off_out),
                 static_cast<float *>(p0), kind, flags, 0u};
     return launch_heads(a, stream);
+}
+
+// ---- the split-bf16 head epilogue (nlspn_heads_x3.h): the entries above with wm as bf16 fragments
+int nlspn_head_x3_packed_size(int C, int nout, int64_t *wm_bf16_elems, int64_t *wv_floats, int64_t *bias_floats) {
+    NLSPN_TRY(nlspn_head_packed_size(C, nout, nullptr, nullptr, nullptr));
+    const int mb = hx3_mb(nout);
+    if (wm_bf16_elems) *wm_bf16_elems = hx3_wm_elems(C, mb);
+    if (wv_floats) *wv_floats = hx3_wv_floats(C);
+    if (bias_floats) *bias_floats = hx3_bias_floats(mb);
+    return NLSPN_OK;
+}
+
+int nlspn_head_x3_pack_weights(const float *w_oa, const float *b_oa, const float *w_id, const float *b_id,
+                               const float *w_cf, const float *b_cf, void *wm, float *wv, float *bias, int C, int nout,
+                               void *stream) {
+    int64_t nm = 0, nv = 0, nb = 0;
+    NLSPN_TRY(nlspn_head_x3_packed_size(C, nout, &nm, &nv, &nb));
+    if (!w_oa || !wm || !wv || !bias) return fail(NLSPN_EINVAL, "head epilogue: null pointer");
+    HeadsPackArgs a{w_oa, b_oa, w_id, b_id, w_cf, b_cf, static_cast<float *>(wm), wv, bias, C, nout, (int)nb};
+    const long long n = nm + nv + nb;
+    void *args[] = {&a};
+    return launch_kernel(reinterpret_cast<const void *>(&headsx3_pack_kernel), dim3((unsigned)((n + 255) / 256)), dim3(256),
+                         args, 0, as_stream(stream), "nlspn_head_x3_pack_weights");
+}
+
+int nlspn_head_epilogue_x3(int dtype, const void *fe1, const void *fd_oa, const void *fd_id, const void *fd_cf,
+                           const void *wm, const float *wv, const float *bias, void *off_aff, void *pred_init,
+                           void *conf, int B, int C, int H, int W, int nout, void *stream) {
+    NLSPN_TRY(check_f32(dtype, "head epilogue"));
+    NLSPN_TRY(check_nonempty(B, H, W));
+    NLSPN_TRY(nlspn_head_packed_size(C, nout, nullptr, nullptr, nullptr));
+    if (!fe1 || !fd_oa || !wm || !wv || !bias || !off_aff) return fail(NLSPN_EINVAL, "head epilogue: null pointer");
+    if ((fd_id == nullptr) != (pred_init == nullptr) || (fd_cf == nullptr) != (conf == nullptr))
+        return fail(NLSPN_EINVAL, "head epilogue: a head's source and output must both be given or both NULL");
+    HeadsArgs a{static_cast<const float *>(fe1), static_cast<const float *>(fd_oa), static_cast<const float *>(fd_id),
+                static_cast<const float *>(fd_cf), static_cast<const float *>(wm), wv, bias,
+                static_cast<float *>(off_aff), static_cast<float *>(pred_init), static_cast<float *>(conf), B, C, H, W,
+                nout, (W + kHdTW - 1) / kHdTW, (H + kHdTH - 1) / kHdTH, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                0u, 0u};
+    return launch_heads_x3(a, stream);
+}
+
+int nlspn_head_epilogue_prologue_x3(int dtype, const void *fe1, const void *fd_oa, const void *fd_id,
+                                    const void *fd_cf, const void *wm, const float *wv, const float *bias,
+                                    const void *dep, const float *gamma, void *pred_init, void *conf_out, void *aff_out,
+                                    void *off_out, void *p0, int B, int C, int H, int W, int kh, int kw, int kind,
+                                    unsigned flags, void *stream) {
+    NLSPN_TRY(check_f32(dtype, "head epilogue"));
+    NLSPN_TRY(check_nonempty(B, H, W));
+    if (kh != 3 || kw != 3)
+        return fail(NLSPN_EUNSUPPORTED, "fused head prologue: 3x3 propagation only (k = %dx%d)", kh, kw);
+    NLSPN_TRY(check_kind(kind));
+    const int nout = 3 * 8;
+    NLSPN_TRY(nlspn_head_packed_size(C, nout, nullptr, nullptr, nullptr));
+    if (!fe1 || !fd_oa || !fd_id || !wm || !wv || !bias || !gamma || !pred_init || !aff_out || !off_out || !p0)
+        return fail(NLSPN_EINVAL, "fused head prologue: null pointer");
+    if ((fd_cf == nullptr) != (conf_out == nullptr))
+        return fail(NLSPN_EINVAL, "fused head prologue: cf_fd1 and conf_out must both be given or both NULL");
+    NLSPN_TRY(check_preserve(flags, dep));
+    HeadsArgs a{static_cast<const float *>(fe1), static_cast<const float *>(fd_oa), static_cast<const float *>(fd_id),
+                static_cast<const float *>(fd_cf), static_cast<const float *>(wm), wv, bias, nullptr,
+                static_cast<float *>(pred_init), static_cast<float *>(conf_out), B, C, H, W, nout,
+                (W + kHdTW - 1) / kHdTW, (H + kHdTH - 1) / kHdTH, static_cast<const float *>(dep), gamma,
+                static_cast<float *>(aff_out), static_cast<float *>(off_out), static_cast<float *>(p0), kind, flags, 0u};
+    return launch_heads_x3(a, stream);
 }
 
 int nlspn_affinity_normalize(int dtype, const void *aff_raw, int64_t aff_bstride, const float *gamma,

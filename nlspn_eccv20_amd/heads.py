@@ -13,6 +13,13 @@ calls it when gradients are off; training keeps the torch convolutions.
 
 The three convolutions' weights are packed once per weight version into the kernel's
 layout (``nlspn_head_pack_weights``) and cached on the module.
+
+``precision="bf16x3"`` (opt-in; default ``"fp32"``) runs the same epilogues on the bf16
+matrix cores with every f32 MFMA operand split into two bf16 parts
+(``nlspn_head_epilogue_x3``, ``csrc/nlspn_heads_x3.h``): weights split when packed, fe1 and
+off_aff_fd1 while staged, three products per term (lo lo dropped), f32 accumulation; the
+one-channel id / cf decoder halves, bias, activations and the fused prologue are the f32
+kernel's code.  ``stats`` counts the launches per precision.
 """
 from __future__ import annotations
 
@@ -23,7 +30,25 @@ import torch.nn as nn
 
 from . import _lib
 
-__all__ = ["head_epilogue", "head_epilogue_prologue", "HeadWeights"]
+__all__ = ["head_epilogue", "head_epilogue_prologue", "HeadWeights", "PRECISIONS", "stats"]
+
+PRECISIONS = ("fp32", "bf16x3")
+# kernel launches per precision (epilogue and fused-prologue entries alike), so a test can prove
+# which kernel ran
+stats = {"fp32": 0, "bf16x3": 0}
+# per precision: (packed-size entry, pack entry, epilogue entry, fused-prologue entry, dtype of wm)
+_ENTRIES = {
+    "fp32": ("nlspn_head_packed_size", "nlspn_head_pack_weights", "nlspn_head_epilogue",
+             "nlspn_head_epilogue_prologue", torch.float32),
+    "bf16x3": ("nlspn_head_x3_packed_size", "nlspn_head_x3_pack_weights", "nlspn_head_epilogue_x3",
+               "nlspn_head_epilogue_prologue_x3", torch.bfloat16),
+}
+
+
+def _check_precision(precision):
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be 'fp32' or 'bf16x3', got {precision!r}")
+    return precision
 
 
 def _conv_of(m):
@@ -39,8 +64,8 @@ class _Packed:
 
 
 class HeadWeights:
-    """The packed weights of (off_aff_dec0, id_dec0, cf_dec0), one entry per device,
-    rebuilt when any of the convolutions' parameters change (storage pointer or tensor
+    """The packed weights of (off_aff_dec0, id_dec0, cf_dec0), one entry per (device,
+    precision), rebuilt when any of the convolutions' parameters change (storage pointer or tensor
     version counter).  An entry is never mutated after it is built, so DataParallel
     replicas sharing this cache from their threads each get their own device's entry."""
 
@@ -60,7 +85,8 @@ class HeadWeights:
         if conv.weight.dtype != torch.float32 or not conv.weight.is_cuda:
             raise RuntimeError(f"{name} weights must be float32 CUDA tensors")
 
-    def get(self, oa, idc, cfc) -> _Packed:
+    def get(self, oa, idc, cfc, precision="fp32") -> _Packed:
+        size_fn, pack_fn, _, _, wm_dtype = _ENTRIES[_check_precision(precision)]
         self._check(oa, "off_aff_dec0")
         self._check(idc, "id_dec0", 1)
         self._check(cfc, "cf_dec0", 1)
@@ -71,24 +97,62 @@ class HeadWeights:
         params = [t for c in (oa, idc, cfc) if c is not None for t in (c.weight, c.bias)]
         key = (tuple((t.data_ptr(), t._version) for t in params), idc is None, cfc is None)
         dev = oa.weight.device
-        e = self._entries.get(dev)
+        e = self._entries.get((dev, precision))
         if e is not None and e.key == key:
             return e
         C, nout = C2 // 2, oa.out_channels
         lib = _lib.get()
         nm, nv, nb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(lib.nlspn_head_packed_size(C, nout, ctypes.byref(nm), ctypes.byref(nv), ctypes.byref(nb)))
+        _lib.check(getattr(lib, size_fn)(C, nout, ctypes.byref(nm), ctypes.byref(nv), ctypes.byref(nb)))
         e = _Packed()
-        e.wm = torch.empty(nm.value, dtype=torch.float32, device=dev)
+        e.wm = torch.empty(nm.value, dtype=wm_dtype, device=dev)
         e.wv = torch.empty(nv.value, dtype=torch.float32, device=dev)
         e.bias = torch.empty(nb.value, dtype=torch.float32, device=dev)
         w = lambda c: None if c is None else c.weight.detach().contiguous()  # noqa: E731
         b = lambda c: None if c is None else c.bias.detach().contiguous()  # noqa: E731
         e.keep = [w(oa), b(oa), w(idc), b(idc), w(cfc), b(cfc)]  # alive until the pack kernel has run
-        _lib.call("nlspn_head_pack_weights", dev, *e.keep, e.wm, e.wv, e.bias, C, nout, _lib.STREAM)
+        _lib.call(pack_fn, dev, *e.keep, e.wm, e.wv, e.bias, C, nout, _lib.STREAM)
         e.key, e.C, e.nout = key, C, nout
-        self._entries[dev] = e
+        self._entries[(dev, precision)] = e
         return e
+
+
+def _mb(nout):
+    """M-blocks of nout + 2 columns (hx3_mb, csrc/nlspn_heads_x3_plan.h): 1, 2, 3 or 5."""
+    mb = (nout + 2 + 31) // 32
+    if mb > 5:
+        raise ValueError(f"nout={nout} (at most 158)")
+    return mb if mb <= 3 else 5
+
+
+def pack_wm_x3_reference(oa, idc=None, cfc=None):
+    """What nlspn_head_x3_pack_weights writes into wm, built with torch on the weights' device
+    (the tests' yardstick for the pack kernel; not on the hot path): bf16
+    [source 2][chunk C/16][tap 9][M-block][part 2][lane 64][8], lane (l32, h) of M-block m
+    holding column 32 m + l32, channels 16 chunk + 8 h + j; part 0 = rne_bf16(w), part 1 =
+    rne_bf16(w - hi).  Columns: 0..nout-1 off_aff_dec0, nout id_dec0 and nout + 1 cf_dec0
+    (source 0 = fe1 only), zeros past them."""
+    C, nout = oa.in_channels // 2, oa.out_channels
+    mb = _mb(nout)
+    w = oa.weight.detach().float()
+    dense = torch.zeros((2, C, 9, 32 * mb), dtype=torch.float32, device=w.device)  # [s][c][t][co]
+    dense[0, :, :, :nout] = w[:, C:].reshape(nout, C, 9).permute(1, 2, 0)
+    dense[1, :, :, :nout] = w[:, :C].reshape(nout, C, 9).permute(1, 2, 0)
+    for k, c in enumerate((idc, cfc)):
+        if c is not None:
+            dense[0, :, :, nout + k] = c.weight.detach().float()[0, C:].reshape(C, 9)
+    hi = dense.to(torch.bfloat16)
+    lo = (dense - hi.float()).to(torch.bfloat16)
+    parts = torch.stack((hi, lo), 0).view(2, 2, C // 16, 2, 8, 9, mb, 32)  # [part][s][chunk][h][j][t][m][l32]
+    return parts.permute(1, 2, 5, 6, 0, 3, 7, 4).contiguous().view(-1)
+
+
+def unpack_wm_x3(wm, C, nout):
+    """(hi, lo) of a packed wm as dense bf16 [source 2][C][tap 9][32 MB columns]."""
+    mb = _mb(nout)
+    v = wm.view(2, C // 16, 9, mb, 2, 2, 32, 8).permute(4, 0, 1, 5, 7, 2, 3, 6)  # [part][s][chunk][h][j][t][m][l32]
+    v = v.reshape(2, 2, C, 9, 32 * mb)
+    return v[0], v[1]
 
 
 def _sources(fe1, off_aff_fd1, id_fd1, cf_fd1, bad):
@@ -102,14 +166,15 @@ def _sources(fe1, off_aff_fd1, id_fd1, cf_fd1, bad):
 
 
 def head_epilogue(fe1, off_aff_fd1, off_aff_dec0, id_fd1=None, id_dec0=None, cf_fd1=None, cf_dec0=None,
-                  weights: HeadWeights | None = None):
+                  weights: HeadWeights | None = None, precision: str = "fp32"):
     """(pred_init, off_aff, confidence) of nlspnmodel.py:297-315 from the decoder outputs.
     ``id_fd1``/``id_dec0`` and ``cf_fd1``/``cf_dec0`` may be None (that head is skipped
-    and None returned for it)."""
+    and None returned for it).  ``precision``: "fp32" or "bf16x3" (module docstring)."""
+    entry = _ENTRIES[_check_precision(precision)][2]
     oa, idc, cfc = _conv_of(off_aff_dec0), _conv_of(id_dec0), _conv_of(cf_dec0)
     if (id_fd1 is None) != (idc is None) or (cf_fd1 is None) != (cfc is None):
         raise RuntimeError("each head needs both its decoder output and its convolution")
-    weights = (weights or HeadWeights()).get(oa, idc, cfc)  # this device's packed entry
+    weights = (weights or HeadWeights()).get(oa, idc, cfc, precision)  # this device's packed entry
     B, C, H, W = fe1.shape
     if C != weights.C:
         raise RuntimeError(f"fe1 has {C} channels, the head convolutions expect {weights.C} + {weights.C}")
@@ -120,20 +185,22 @@ def head_epilogue(fe1, off_aff_fd1, off_aff_dec0, id_fd1=None, id_dec0=None, cf_
     off_aff = torch.empty((B, weights.nout, H, W), dtype=torch.float32, device=dev)
     pred_init = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev) if id_fd1 is not None else None
     conf = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev) if cf_fd1 is not None else None
-    _lib.call("nlspn_head_epilogue", dev, _lib.DTYPE_F32, *srcs, weights.wm, weights.wv, weights.bias, off_aff,
+    _lib.call(entry, dev, _lib.DTYPE_F32, *srcs, weights.wm, weights.wv, weights.bias, off_aff,
               pred_init, conf, B, C, H, W, weights.nout, _lib.STREAM)
+    stats[precision] += 1
     return pred_init, off_aff, conf
 
 
 def head_epilogue_prologue(fe1, off_aff_fd1, off_aff_dec0, id_fd1, id_dec0, dep, gamma, affinity="TGASS",
                            cf_fd1=None, cf_dec0=None, preserve_input=True, always_clip=False,
-                           weights: HeadWeights | None = None) -> dict:
+                           weights: HeadWeights | None = None, precision: str = "fp32") -> dict:
     """The three head convolutions with the propagation prologue fused into their
     epilogue (3x3, K = 8, offsets on; nlspnmodel.py:297-348): returns {'pred_init',
     'offset' (_off_insert, :324), 'aff' (normalised + reference tap, :325),
     'confidence' (blended, :328-334, or None), 'p0' (iteration 1's input, :341-348)} —
     what nlspn_propagate's step 1 would produce from the raw head outputs, bit for bit.
-    Feed them to propagation.propagate_normalized."""
+    Feed them to propagation.propagate_normalized.  ``precision`` as head_epilogue's."""
+    entry = _ENTRIES[_check_precision(precision)][3]
     oa, idc, cfc = _conv_of(off_aff_dec0), _conv_of(id_dec0), _conv_of(cf_dec0)
     if (cf_fd1 is None) != (cfc is None) or id_fd1 is None or idc is None:
         raise RuntimeError("the fused prologue needs id_fd1/id_dec0, and cf_fd1 with cf_dec0")
@@ -141,7 +208,7 @@ def head_epilogue_prologue(fe1, off_aff_fd1, off_aff_dec0, id_fd1, id_dec0, dep,
         raise RuntimeError("the fused prologue is the 3x3 / K=8 / offset geometry (off_aff_dec0 -> 24 channels)")
     if affinity not in _lib.AFF_KINDS:
         raise NotImplementedError(affinity)
-    weights = (weights or HeadWeights()).get(oa, idc, cfc)
+    weights = (weights or HeadWeights()).get(oa, idc, cfc, precision)
     B, C, H, W = fe1.shape
     srcs = _sources(fe1, off_aff_fd1, id_fd1, cf_fd1,
                     lambda n, t, shape: f"{n} must be a float32 CUDA tensor of shape {shape}")
@@ -153,7 +220,8 @@ def head_epilogue_prologue(fe1, off_aff_fd1, off_aff_dec0, id_fd1, id_dec0, dep,
     e = lambda c: torch.empty((B, c, H, W), dtype=torch.float32, device=dev)  # noqa: E731
     out = {"pred_init": e(1), "offset": e(18), "aff": e(9), "confidence": e(1) if cf_fd1 is not None else None,
            "p0": e(1)}
-    _lib.call("nlspn_head_epilogue_prologue", dev, _lib.DTYPE_F32, *srcs, weights.wm, weights.wv, weights.bias, dep, g,
+    _lib.call(entry, dev, _lib.DTYPE_F32, *srcs, weights.wm, weights.wv, weights.bias, dep, g,
               out["pred_init"], out["confidence"], out["aff"], out["offset"], out["p0"],
               B, C, H, W, 3, 3, _lib.AFF_KINDS[affinity], _lib.flags(preserve_input, always_clip), _lib.STREAM)
+    stats[precision] += 1
     return out

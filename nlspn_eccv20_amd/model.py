@@ -26,6 +26,7 @@ import torch.nn as nn
 from .propagation import (affinity_normalization, kernel_geometry, off_insert, prop_step, propagate,
                           propagate_normalized)
 from .gru import GruConvs
+from .heads import PRECISIONS as HEAD_PRECISIONS
 from .heads import HeadWeights, head_epilogue, head_epilogue_prologue
 from .s2d import s2d_front
 
@@ -248,6 +249,11 @@ class NLSPNModel(nn.Module):
         if args.use_S2D:
             self.S2D = S2D()
         self._head_weights = HeadWeights()  # packed head-epilogue weights (a cache, not state)
+        # head_precision = "bf16x3": at inference, where the fused head kernel runs, the three head
+        # convolutions on the bf16 matrix cores with split operands (heads.py, nlspn_heads_x3.h,
+        # DESIGN.md 3.7.1).  "fp32" (default) is the f32 kernel, bit for bit; ignored under
+        # gradients and on the CPU, where the torch convolutions run
+        self.head_precision = "fp32"
         # GRU mode: encode_dep / encode_aff / ConvGRU / decode_aff as HIP convolutions (gru.py),
         # at inference and, with native_gru_train, under gradients (their HIP backward:
         # nlspn_gconv_bwd.h; off by default: slower than the tuned modules);
@@ -279,6 +285,16 @@ class NLSPNModel(nn.Module):
         if value not in ("fp32", "fp16", "bf16x3"):
             raise ValueError(f"gru_precision must be 'fp32', 'fp16' or 'bf16x3', got {value!r}")
         object.__setattr__(self, "_gru_precision", value)
+
+    @property
+    def head_precision(self) -> str:
+        return self._head_precision
+
+    @head_precision.setter
+    def head_precision(self, value):
+        if value not in HEAD_PRECISIONS:
+            raise ValueError(f"head_precision must be 'fp32' or 'bf16x3', got {value!r}")
+        object.__setattr__(self, "_head_precision", value)
 
     @property
     def gru_wgrad_precision(self) -> str:
@@ -362,7 +378,8 @@ class NLSPNModel(nn.Module):
             # inference: the three last convolutions + bias/activation as one HIP kernel
             # reading fe1 and the decoder outputs in place (heads.py, nlspn_heads.h)
             return head_epilogue(fe1, off_aff_fd1, self.off_aff_dec0, id_fd1, self.id_dec0, cf_fd1,
-                                 self.cf_dec0 if self.args.conf_prop else None, weights=self._head_cache())
+                                 self.cf_dec0 if self.args.conf_prop else None, weights=self._head_cache(),
+                                 precision=self.head_precision)
         pred_init = self.id_dec0(torch.cat((id_fd1, fe1), 1))
         off_aff = self.off_aff_dec0(torch.cat((off_aff_fd1, fe1), 1))
         confidence = None
@@ -422,7 +439,7 @@ class NLSPNModel(nn.Module):
         h = head_epilogue_prologue(fe1, off_aff_fd1, self.off_aff_dec0, id_fd1, self.id_dec0, dep,
                                    self.aff_scale_const, a.affinity, cf_fd1,
                                    self.cf_dec0 if a.conf_prop else None, a.preserve_input, a.always_clip,
-                                   weights=self._head_cache())
+                                   weights=self._head_cache(), precision=self.head_precision)
         o = propagate_normalized(h["p0"], dep if a.preserve_input else None, h["confidence"], h["aff"],
                                  h["offset"], a.prop_time, (3, 3), a.preserve_input, a.always_clip)
         return {"pred": o["pred"], "pred_init": h["pred_init"], "pred_inter": o["pred_inter"],
