@@ -7,6 +7,9 @@ fp16.  An fp16 x fp16 product and an fp16 -> fp32 conversion are exact, so the k
 fp32 arithmetic on fp16 inputs is the oracle's fp32 arithmetic on those values; the
 reference tap's weight is 1 - (sum of the fp16 affinities in tap order) in fp32, so the
 oracle is given that plane (nlspnmodel.py:262-263).
+The same bar holds on the grid-and-ramp inputs of tests/_fwd_cases.py rounded to fp16 (taps on
+integer coordinates, on -1, H - 1 and H, in the rims, and at every half-integer distance up to
+30 cells: on and beyond every edge of the LDS window).
 Reference: modulated_deform_im2col_cuda.cuh:127-194 (sampling, validity test :180).
 """
 import numpy as np
@@ -75,6 +78,37 @@ def test_step_fp16_bitexact_vs_oracle(oracle, B, H, W, kh, kw, sigma, with_conf)
     out = prop_step(cu(p, h), cu(conf, h), cu(dep, h), cu(aff, h), cu(off_ins, h), kernel=(kh, kw))
     assert out.dtype == h
     np.testing.assert_array_equal(out.cpu().numpy(), exp)
+
+
+@pytest.mark.parametrize("name", ["g24x40", "k17", "k5x5"])
+@pytest.mark.parametrize("with_conf", [True, False])
+def test_step_fp16_bitexact_on_grid_and_ramp_inputs(oracle, name, with_conf):
+    """One fp16 step on the tap classes and the ramp image (tests/_fwd_cases.py), every plane rounded
+    to fp16: fp16 values, float32 arithmetic, the reference tap from the fp16 affinities."""
+    import _fwd_cases as fc
+    c = fc.INPUTS[name]
+    kh, kw = c["kh"], c["kw"]
+    K = kh * kw - 1
+    s = fc.inputs(name)
+    p, conf = fc.prologue(name, s)
+    aff = oracle.affinity_normalization(s["aff"], c["kind"], fc.gamma_of(name))
+    p, dep, conf, aff, off_ins = (f16(x) for x in (p, s["dep"], conf, aff, oracle.off_insert(s["off"])))  # (copies)
+    ref = K // 2
+    acc = np.zeros(p.shape[:1] + p.shape[2:], np.float32)
+    for k in range(K + 1):
+        if k != ref:
+            acc = acc + aff[:, k]
+    aff[:, ref] = np.float32(1.0) - acc  # the kernel's reference-tap weight, same order
+    if not with_conf:
+        conf = None
+    exp = _oracle_step(oracle, p, conf, dep, aff, off_ins, kh, kw).astype(np.float16)
+    h = torch.float16
+    out = prop_step(cu(p, h), cu(conf, h), cu(dep, h), cu(aff, h), cu(off_ins, h), kernel=(kh, kw))
+    assert out.dtype == h
+    got = out.cpu().numpy()
+    bad = got.view(np.uint16) != exp.view(np.uint16)
+    assert not bad.any(), (int(bad.sum()), [tuple(int(v) for v in i) for i in np.argwhere(bad)[:8]],
+                           "the ramp image is item %d" % c["B"])
 
 
 @pytest.mark.parametrize("half", [False, True])
