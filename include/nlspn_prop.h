@@ -527,6 +527,15 @@ int nlspn_gconv_affnorm(const float *x0, int c0, const float *wpk, const float *
  * nlspn_gconv_wgrad_bf16x3_workspace_bytes.  Nothing is clamped (an inf operand gives NaN).
  * Shapes with both channel counts <= 16 are forwarded to nlspn_gconv_wgrad, bit for bit.
  *
+ * nlspn_gconv_wgrad_narrow (opt-in; csrc/nlspn_gwnarrow.h): the same call, arguments and
+ * validation for the stride-2 layers whose channel counts are both <= 16 and whose large tensor
+ * is one source (nlspn_gconv_wgrad_narrow_covers(stride, Cs, c0, c1) = 1): exact f32 products
+ * and f32 sums by a kernel that streams each large row once, with db from the operand it has
+ * staged, and one two-level fixed-order reduce: two launches, no atomics, bit-reproducible, the
+ * bits a function of the shape alone.  Operands need 4-byte alignment only.  Any other shape
+ * is forwarded to nlspn_gconv_wgrad, bit for bit; nlspn_gconv_wgrad_narrow_workspace_bytes is
+ * then that entry's size.
+ *
  * ConvGRU: nlspn_gconv_gru_train is the NLSPN_GC_GRU1 (stage 1: x0 = h, x1 = x, also stores r
  * into rb) / NLSPN_GC_GRU2 (stage 2: x0 = r*h, also stores q into qb) launch of nlspn_gconv,
  * bit-identical in its other outputs.  nlspn_gconv_gru_gates_backward: stage 1 du_q = dh' z
@@ -548,6 +557,11 @@ int nlspn_gconv_wgrad(int stride, const float *s, int Cs, const float *l0, int c
                       int Hs, int Ws, int Hl, int Wl, void *stream);
 size_t nlspn_gconv_wgrad_bf16x3_workspace_bytes(int stride, int Cs, int Cl, int B, int Hs, int Ws, int Hl, int Wl);
 int nlspn_gconv_wgrad_bf16x3(int stride, const float *s, int Cs, const float *l0, int c0, const float *l1, int c1,
+                             float *dw, float *db, int bias_from_large, float scale, void *workspace,
+                             int64_t workspace_bytes, int B, int Hs, int Ws, int Hl, int Wl, void *stream);
+int nlspn_gconv_wgrad_narrow_covers(int stride, int Cs, int c0, int c1);
+size_t nlspn_gconv_wgrad_narrow_workspace_bytes(int stride, int Cs, int Cl, int B, int Hs, int Ws, int Hl, int Wl);
+int nlspn_gconv_wgrad_narrow(int stride, const float *s, int Cs, const float *l0, int c0, const float *l1, int c1,
                              float *dw, float *db, int bias_from_large, float scale, void *workspace,
                              int64_t workspace_bytes, int B, int Hs, int Ws, int Hl, int Wl, void *stream);
 int nlspn_gconv_gru_train(int stage, const float *x0, const float *x1, int c1, const float *wpk, const float *bias,

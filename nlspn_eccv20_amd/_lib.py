@@ -93,6 +93,10 @@ SIGNATURES = {
     "nlspn_gconv_wgrad_bf16x3_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "nlspn_gconv_wgrad_bf16x3": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, ctypes.c_float, _vp, _i64, _i, _i, _i,
                                       _i, _i, _vp]),
+    "nlspn_gconv_wgrad_narrow_covers": (_i, [_i, _i, _i, _i]),
+    "nlspn_gconv_wgrad_narrow_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "nlspn_gconv_wgrad_narrow": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, ctypes.c_float, _vp, _i64, _i, _i, _i,
+                                      _i, _i, _vp]),
     "nlspn_gconv_gru_train": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
                                    _vp]),
     "nlspn_gconv_gru_gates_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -111,7 +115,9 @@ AB_OPTIONAL = frozenset({"nlspn_resident_status", "nlspn_resident_config", "nlsp
                          "nlspn_gconv_wgrad", "nlspn_gconv_gru_train", "nlspn_gconv_gru_gates_backward",
                          "nlspn_gconv16_pack_layout", "nlspn_gconv16",
                          "nlspn_gconv_x3_pack_layout", "nlspn_gconv_x3",
-                         "nlspn_gconv_wgrad_bf16x3_workspace_bytes", "nlspn_gconv_wgrad_bf16x3"})
+                         "nlspn_gconv_wgrad_bf16x3_workspace_bytes", "nlspn_gconv_wgrad_bf16x3",
+                         "nlspn_gconv_wgrad_narrow_covers", "nlspn_gconv_wgrad_narrow_workspace_bytes",
+                         "nlspn_gconv_wgrad_narrow"})
 
 _lib = None
 

@@ -7,6 +7,7 @@
 #include "nlspn_gconv16.h"
 #include "nlspn_gconv_x3.h"
 #include "nlspn_gwgrad16.h"
+#include "nlspn_gwnarrow.h"
 
 namespace nlspn {
 // defined in nlspn_kern_gconv.hip
@@ -28,6 +29,9 @@ extern template __global__ void gsmallx3_kernel<16>(GconvX3Args, const float *);
 // defined in nlspn_kern_gwgrad16.hip
 #define NLSPN_GW16_EXTERN(...) extern template __global__ void gwgrad16_kernel<__VA_ARGS__>(GwgradArgs);
 NLSPN_GW16_CONFIGS(NLSPN_GW16_EXTERN)
+// defined in nlspn_kern_gwnarrow.hip
+#define NLSPN_GWN_EXTERN(NB) extern template __global__ void gwnarrow_kernel<NB>(GwnArgs);
+NLSPN_GWN_BLOCKS(NLSPN_GWN_EXTERN)
 }  // namespace nlspn
 
 using namespace nlspn;
@@ -395,6 +399,47 @@ int nlspn_gconv_wgrad_bf16x3(int stride, const float *s, int Cs, const float *l0
     GwgradArgs a = gw_args(s, Cs, l0, c0, l1, c1, workspace, B, Hs, Ws, Hl, Wl, pl);
     return gw_launch(fn, pl.g.nthr(), pl.g.lds_bytes(), pl.g.nt(), a, pl, dw, db, bias_from_large, scale, stream,
                      NLSPN_GW_LABELS("nlspn_gconv_wgrad_bf16x3"));
+}
+
+// ---- the streaming weight gradient of the narrow layers (nlspn_gwnarrow.h)
+int nlspn_gconv_wgrad_narrow_covers(int stride, int Cs, int c0, int c1) { return gwn_covers(stride, Cs, c0, c1) ? 1 : 0; }
+
+size_t nlspn_gconv_wgrad_narrow_workspace_bytes(int stride, int Cs, int Cl, int B, int Hs, int Ws, int Hl, int Wl) {
+    if (gw_check_shape(stride, Cs, Cl, B, Hs, Ws, Hl, Wl)) return 0;
+    if (!gwn_covers(stride, Cs, Cl, 0)) return nlspn_gconv_wgrad_workspace_bytes(stride, Cs, Cl, B, Hs, Ws, Hl, Wl);
+    return (size_t)gwn_plan(Cs, Cl, B, Hs, Ws, Hl, Wl).floats * sizeof(float);
+}
+
+int nlspn_gconv_wgrad_narrow(int stride, const float *s, int Cs, const float *l0, int c0, const float *l1, int c1,
+                             float *dw, float *db, int bias_from_large, float scale, void *workspace,
+                             int64_t workspace_bytes, int B, int Hs, int Ws, int Hl, int Wl, void *stream) {
+    NLSPN_TRY(gw_check_call(stride, s, Cs, l0, c0, l1, c1, dw, db, bias_from_large, workspace, B, Hs, Ws, Hl, Wl));
+    // a shape the streaming kernel does not cover: the f32 entry, bit for bit
+    if (!gwn_covers(stride, Cs, c0, c1))
+        return nlspn_gconv_wgrad(stride, s, Cs, l0, c0, l1, c1, dw, db, bias_from_large, scale, workspace, workspace_bytes,
+                                 B, Hs, Ws, Hl, Wl, stream);
+    const GwnPlan pl = gwn_plan(Cs, c0, B, Hs, Ws, Hl, Wl);
+    NLSPN_TRY(gw_check_workspace(workspace_bytes, pl.floats));
+    const void *fn = nullptr;
+#define NLSPN_GWN_PICK(NB) if (pl.nb == NB) fn = reinterpret_cast<const void *>(&gwnarrow_kernel<NB>);
+    NLSPN_GWN_BLOCKS(NLSPN_GWN_PICK)
+    if (!fn) return fail(NLSPN_EUNSUPPORTED, "gconv wgrad narrow: no kernel for %d blocks", pl.nb);
+    GwnArgs a{};
+    a.s = s; a.l = l0; a.ws = static_cast<float *>(workspace);
+    a.Cs = Cs; a.Cl = c0; a.B = B; a.Hs = Hs; a.Ws = Ws; a.Hl = Hl; a.Wl = Wl;
+    a.nbands = pl.nbands; a.bw = pl.bw; a.ngroups = pl.ngroups; a.units = pl.units; a.ups = pl.ups;
+    a.bias_from_large = bias_from_large ? 1 : 0;
+    a.slab = pl.slab;
+    hipStream_t st = as_stream(stream);
+    NLSPN_TRY(set_lds_attr(fn, pl.lds_bytes));
+    void *args[] = {&a};
+    NLSPN_TRY(launch_kernel(fn, dim3((unsigned)pl.nsl), dim3(kGwnNTHR), args, (size_t)pl.lds_bytes, st, "nlspn_gconv_wgrad_narrow"));
+    const float *wsp = a.ws;
+    int Cl = c0, nbias = !db ? 0 : bias_from_large ? Cl : Cs, nsl = pl.nsl, nb = pl.nb;
+    long long slab = pl.slab;
+    void *rargs[] = {&wsp, &dw, &db, &Cs, &Cl, &nbias, &nsl, &slab, &nb, &scale};
+    return launch_kernel(reinterpret_cast<const void *>(&gwnarrow_reduce_kernel), dim3((unsigned)((Cs * 9 * Cl + 15) / 16 + (db ? 1 : 0))),
+                         dim3(256), rargs, 0, st, "nlspn_gconv_wgrad_narrow reduce");
 }
 
 int nlspn_gconv_dgrad(int layer, const float *g, int cg, const float *wpk, const float *ysave, const float *add0,

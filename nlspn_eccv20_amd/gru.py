@@ -58,6 +58,13 @@ Opt-in under gradients (``GruConvs.wgrad_precision = "bf16x3"``, set through
 ``NLSPNModel.gru_wgrad_precision``) the weight gradients run on the bf16 matrix cores with each
 f32 operand split into two bf16 parts (``nlspn_gconv_wgrad_bf16x3``, ``csrc/nlspn_gwgrad16.h``);
 everything else of the backward is the same launches, and ``stats["wgrad_x3"]`` counts them.
+
+Opt-in under gradients as well (``GruConvs.wgrad_narrow = True``, set through
+``NLSPNModel.gru_wgrad_narrow``): the weight gradients of the stride-2 layers whose channel
+counts are both <= 16 (1 / 9 -> 16 and 16 -> 8; ``nlspn_gconv_wgrad_narrow_covers``) take the
+streaming kernel (``nlspn_gconv_wgrad_narrow``, ``csrc/nlspn_gwnarrow.h``: exact f32 products,
+two launches per call, the bias gradient from the staged operand), whatever ``wgrad_precision``
+is; every other layer keeps its entry and its bits.  ``stats["wgrad_narrow"]`` counts its launches.
 """
 from __future__ import annotations
 
@@ -429,6 +436,9 @@ class GruConvs:
         # "bf16x3": the weight gradients on the bf16 matrix cores with split operands
         # (nlspn_gconv_wgrad_bf16x3, csrc/nlspn_gwgrad16.h); "fp32" (default): nlspn_gconv_wgrad
         self.wgrad_precision = "fp32"
+        # True: the layers nlspn_gconv_wgrad_narrow_covers accepts (stride 2, both channel counts
+        # <= 16) take nlspn_gconv_wgrad_narrow (csrc/nlspn_gwnarrow.h), whatever wgrad_precision is
+        self.wgrad_narrow = False
         self.reset_stats()
 
     def reset_stats(self):
@@ -436,9 +446,10 @@ class GruConvs:
         ``wgrad`` (kernel launches of the weight / bias gradients) and ``gates_bwd``; ``gru_fwd``
         counts ConvGRU cell forwards; ``fwd16`` the forward launches of the f16-operand family;
         ``wgrad_x3`` the weight / bias gradient launches of the ``"bf16x3"`` mode, counted as
-        ``wgrad`` counts the f32 entry's; ``fwd_x3`` the forward launches of the split-bf16 family."""
+        ``wgrad`` counts the f32 entry's; ``fwd_x3`` the forward launches of the split-bf16 family;
+        ``wgrad_narrow`` the launches of the narrow layers' streaming entry (two per call)."""
         self.stats = {"fwd": 0, "dgrad": 0, "wgrad": 0, "gates_bwd": 0, "gru_fwd": 0, "fwd16": 0, "wgrad_x3": 0,
-                      "fwd_x3": 0}
+                      "fwd_x3": 0, "wgrad_narrow": 0}
 
     @staticmethod
     def supported(model) -> bool:
@@ -728,14 +739,20 @@ class GruConvs:
 
     def _wgrad_raw(self, stride, s, l0, l1, bias_from_large, scale):
         """(dW (Cs, Cl, 3, 3), db) of nlspn_gconv_wgrad (wgrad_precision = "bf16x3": of
-        nlspn_gconv_wgrad_bf16x3): s the small tensor, l0 (+ l1) the large one."""
+        nlspn_gconv_wgrad_bf16x3; wgrad_narrow and a shape nlspn_gconv_wgrad_narrow_covers accepts:
+        of nlspn_gconv_wgrad_narrow): s the small tensor, l0 (+ l1) the large one."""
         if self.wgrad_precision not in ("fp32", "bf16x3"):
             raise ValueError(f"wgrad_precision must be 'fp32' or 'bf16x3', got {self.wgrad_precision!r}")
+        if not isinstance(self.wgrad_narrow, bool):
+            raise ValueError(f"wgrad_narrow must be a bool, got {self.wgrad_narrow!r}")
         x3 = self.wgrad_precision == "bf16x3"
         name = "nlspn_gconv_wgrad_bf16x3" if x3 else "nlspn_gconv_wgrad"
         lib = _lib.get()
         B, Cs, Hs, Ws = s.shape
         c0, c1 = l0.shape[1], 0 if l1 is None else l1.shape[1]
+        narrow = self.wgrad_narrow and bool(lib.nlspn_gconv_wgrad_narrow_covers(stride, Cs, c0, c1))
+        if narrow:
+            name = "nlspn_gconv_wgrad_narrow"
         Hl, Wl = l0.shape[2:]
         need = getattr(lib, name + "_workspace_bytes")(stride, Cs, c0 + c1, B, Hs, Ws, Hl, Wl)
         key = (s.device, torch.cuda.current_stream(s.device).cuda_stream)
@@ -746,5 +763,8 @@ class GruConvs:
         db = torch.empty(c0 if bias_from_large else Cs, device=s.device, dtype=torch.float32)
         _lib.call(name, s.device, stride, s, Cs, l0, c0, l1, c1, dw, db, int(bias_from_large), scale,
                   ws, ws.numel() * 4, B, Hs, Ws, Hl, Wl, _lib.STREAM)
-        self.stats["wgrad_x3" if x3 else "wgrad"] += 4
+        if narrow:
+            self.stats["wgrad_narrow"] += 2
+        else:
+            self.stats["wgrad_x3" if x3 else "wgrad"] += 4
         return dw, db

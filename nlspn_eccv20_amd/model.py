@@ -273,6 +273,11 @@ class NLSPNModel(nn.Module):
         # (csrc/nlspn_gwgrad16.h); forward, data gradients and gate derivatives
         # are unchanged.  "fp32" (default) is the path above, bit for bit; ignored everywhere else
         self.gru_wgrad_precision = "fp32"
+        # gru_wgrad_narrow = True: where the native training path runs, the weight gradients of the
+        # narrow stride-2 layers (1 / 9 -> 16, 16 -> 8) by the streaming kernel (csrc/nlspn_gwnarrow.h,
+        # DESIGN.md 3.8.5), whatever gru_wgrad_precision is; every other launch is unchanged.  False
+        # (default) is the path above, bit for bit; ignored at inference and without native_gru_train
+        self.gru_wgrad_narrow = False
         params = nn.ParameterList([p for p in self.parameters() if p.requires_grad])
         self.param_groups = [{"params": params, "lr": args.lr}]
 
@@ -305,6 +310,16 @@ class NLSPNModel(nn.Module):
         if value not in ("fp32", "bf16x3"):
             raise ValueError(f"gru_wgrad_precision must be 'fp32' or 'bf16x3', got {value!r}")
         self._gru_convs.wgrad_precision = value
+
+    @property
+    def gru_wgrad_narrow(self) -> bool:
+        return self._gru_convs.wgrad_narrow
+
+    @gru_wgrad_narrow.setter
+    def gru_wgrad_narrow(self, value):
+        if not isinstance(value, bool):
+            raise ValueError(f"gru_wgrad_narrow must be a bool, got {value!r}")
+        self._gru_convs.wgrad_narrow = value
 
     def _gru_fp16(self, x) -> bool:
         """The f16-operand convolutions run: asked for, gradients off, and the HIP path would run."""
