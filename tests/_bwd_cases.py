@@ -73,6 +73,8 @@ CASES = {
     "step_op": _case(2, 24, 40, 5, seed=21, form="step_op"),
     "range": _case(2, 48, 64, 2, seed=22, special="range"),
     "nonexact": _case(2, 24, 40, 3, seed=23, special="nonexact"),
+    # the compact batch of tests/_big_cases.py: the non-zero images of its periodic and sparse batches
+    "big_compact": _case(4, 24, 32, 3, seed=24),
 }
 # images whose first draw(s) fall inside the guard: case -> {image: attempt}
 RETRY = {
@@ -90,6 +92,7 @@ RETRY = {
     "steps_split_manyB": {4: 1, 22: 1, 25: 1, 38: 1, 47: 1, 54: 1, 56: 1, 69: 1, 77: 1, 79: 1, 97: 1, 105: 1,
         134: 1, 135: 2, 148: 1, 157: 1, 191: 1, 192: 1, 214: 1, 229: 1, 254: 1},
     "range": {0: 1, 1: 2},
+    "big_compact": {1: 1},
 }
 for _n, _r in RETRY.items():
     CASES[_n]["retry"] = _r
@@ -339,6 +342,7 @@ R32 = {
     "step_op": {"pred_init": 2.2e-06, "aff": 3.1e-07, "offset": 3.7e-07, "confidence": 1.7e-06, "gamma": 2.2e-10},
     "range": {"pred_init": 7.7e-07, "aff": 8.9e-07, "offset": 1.6e-06, "confidence": 9.2e-07, "gamma": 3.2e-09},
     "nonexact": {"pred_init": 2.2e-06, "aff": 3.2e-07, "offset": 4.3e-07, "confidence": 8.9e-07, "gamma": 8.0e-08},
+    "big_compact": {"pred_init": 2.4e-06, "aff": 3.7e-07, "offset": 4.0e-07, "confidence": 2.0e-06, "gamma": 4.2e-09},
 }
 
 # ------------------------------------------------------------------ DCN (seam 2)

@@ -261,6 +261,15 @@ GATE_CASES = [dict(id="gates-stage1-3x128x5x7", stage=1, B=3, hc=128, H=5, W=7, 
               dict(id="gates-stage0-none", stage=0, B=1, hc=1, H=1, W=3 * 37 * 11, act=ACT_NONE)]
 GATE_BY_ID = {c["id"]: c for c in GATE_CASES}
 
+# The compact batches of tests/test_gpu_big_offsets.py (3 items, hc = 128, 8 x 8): by id only, so that
+# the operand, reference and bar functions below serve them; the per-element tests above keep their lists.
+BIG_GATES = dict(id="gates-big-3x128x8x8", stage=2, B=3, hc=128, H=8, W=8, act=ACT_NONE)
+BIG_DG_Q = _dg(36, 8, 8, B=3, cg=128, cout=256, split=128, tag="-big-convq")
+BIG_DG_ZR = _dg(36, 8, 8, B=3, cg=256, cout=256, split=128, add="alias", tag="-big-convzr")
+GATE_BY_ID[BIG_GATES["id"]] = BIG_GATES
+DG_BY_ID[BIG_DG_Q["id"]] = BIG_DG_Q
+DG_BY_ID[BIG_DG_ZR["id"]] = BIG_DG_ZR
+
 RELU_PLANTS = (0.0, -0.0, 2.0 ** -126, -1.5, -(2.0 ** -126), -0.0)
 TANH_PLANTS = (1.0, -1.0, 1.0 - 2.0 ** -24, -(1.0 - 2.0 ** -24), 1.0 - 2.0 ** -23, -(1.0 - 3 * 2.0 ** -24))
 

@@ -73,6 +73,7 @@ BWD_FORMS = {
     "steps_split_clip": "steps", "steps_split_manyB": "steps",
     "onepass_longT": "onepass", "onepass_env": "onepass", "k17": "onepass", "k5x5": "onepass", "k7x7": "onepass",
     "noffset": "onepass", "range": ("resident", 128, 1), "nonexact": ("resident", 120, 1),
+    "big_compact": ("resident", 64, 1),  # (the compact batch of tests/_big_cases.py; its large batches take the steps)
 }
 
 
