@@ -160,6 +160,64 @@ int nlspn_head_epilogue_prologue_x3(int dtype, const void *fe1, const void *fd_o
                                     int W, int kh, int kw, int kind, unsigned flags, void *stream);
 
 /*
+ * Backward of the head epilogue (training through nlspn_head_epilogue; opt-in;
+ * csrc/nlspn_heads_bwd.h).  Replaces the autograd of src/model/nlspnmodel.py:296-315 — the
+ * three torch.cat copies, their saved copies and MIOpen's convolution backward — by pieces the
+ * caller drives (nlspn_eccv20_amd/heads.py _HeadFn).  f32 NCHW, contiguous, no double
+ * backward.  R = nout + 2 rows in the forward kernel's column order: 0..nout-1 off_aff_dec0,
+ * nout id_dec0, nout + 1 cf_dec0.
+ *
+ * nlspn_head_backward_pre: gpre (B x R x H x W), the pre-activation gradient, in one launch:
+ *   rows < nout = g_off_aff (B x nout x H x W); row nout = g_pred_init where pred_init > 0,
+ *   else 0 (a select: -0.0 and NaN outputs give 0); row nout + 1 = g_conf * (conf * (1 - conf)).
+ *   pred_init, conf: the saved forward outputs (B x 1 x H x W).  Any of the three gradients may
+ *   be NULL (zero rows); pred_init / conf are NULL together with their gradient, else
+ *   NLSPN_EINVAL.  Rows < nout and the ReLU row are copies; the sigmoid row is two f32 products.
+ *
+ * The two wide data gradients are a launch of the existing stride-1 adjoint preset:
+ *   nlspn_gconv_dgrad(NLSPN_GC_DG_S1, gpre, R, wadj, NULL, NULL, NULL, d_fd_oa, d_fe1, C, B, H,
+ *   W, 2 C, H, W, NLSPN_GC_ACT_NONE, 1, stream), wadj the stacked (R, 2C, 3, 3) weight (the
+ *   decoder halves of the id / cf rows zeroed) with taps flipped and channels transposed, packed
+ *   for that preset (gru.py pack_adjoint_s1).
+ *
+ * nlspn_head_dgrad_single: the one-row adjoints on the VALU, d_fd_id[ci] = w_id[0, ci] flipped
+ *   (*) gpre[nout], d_fd_cf[ci] = w_cf[0, ci] flipped (*) gpre[nout + 1] (B x C x H x W each):
+ *   nine fmaf per element in (ky, kx) order, zero outside the image.  w_id / w_cf: the modules'
+ *   own (1, 2C, 3, 3) weights.  A NULL (weight, output) pair skips that head; one of a pair
+ *   alone is NLSPN_EINVAL.
+ *
+ * nlspn_head_wgrad: dW / db of the three convolutions in the modules' own layouts (dw_oa
+ *   (nout, 2C, 3, 3), dw_id / dw_cf (1, 2C, 3, 3), the decoder half first, then fe1; db_oa
+ *   (nout), db_id / db_cf (1)): dW_r[c][t] = sum over b, y, x of gpre[b, r, y, x] * src[b, c,
+ *   y - 1 + ky, x - 1 + kx], zero outside the image, src = fe1 for c >= C and the row's own
+ *   decoder output below; db_r = sum gpre[r].  Every row against [fd_oa | fe1] is an implicit
+ *   GEMM on the f32 matrix cores (exact f32 products, f32 accumulation; rows in tiles of 32, K =
+ *   pixels); the id / cf rows against fd_id / fd_cf are VALU fmaf sums.  K is cut into slices by
+ *   the shape alone; each slice writes f32 partials into the workspace
+ *   (nlspn_head_wgrad_workspace_bytes; 0 for a shape the entry refuses) and further launches sum
+ *   them in slice order: no atomics, no waiting between workgroups, the same bits on every run
+ *   and device.  fd_id / fd_cf are NULL together with their dw / db pair.  Operands need 4-byte
+ *   alignment only.
+ *
+ * Refusals, before any device call and in this order: NULL required pointers or a half-given
+ * pair (NLSPN_EINVAL); C not a positive multiple of 16 (NLSPN_EINVAL); nout < 1 (NLSPN_EINVAL)
+ * or > 158 (NLSPN_EUNSUPPORTED); empty sizes (NLSPN_EINVAL); workspace too small
+ * (NLSPN_EINVAL); "input too large" (NLSPN_EINVAL): one image's C (or R) planes reach 2 GiB,
+ * B * H * W or a unit / workgroup count does not fit an int.
+ */
+int nlspn_head_backward_pre(const float *g_off_aff, const float *g_pred_init, const float *g_conf,
+                            const float *pred_init, const float *conf, float *gpre, int B, int H,
+                            int W, int nout, void *stream);
+int nlspn_head_dgrad_single(const float *gpre, const float *w_id, const float *w_cf,
+                            float *d_fd_id, float *d_fd_cf, int B, int C, int H, int W, int nout,
+                            void *stream);
+size_t nlspn_head_wgrad_workspace_bytes(int B, int C, int H, int W, int nout);
+int nlspn_head_wgrad(const float *gpre, const float *fe1, const float *fd_oa, const float *fd_id,
+                     const float *fd_cf, float *dw_oa, float *db_oa, float *dw_id, float *db_id,
+                     float *dw_cf, float *db_cf, void *workspace, int64_t workspace_bytes, int B,
+                     int C, int H, int W, int nout, void *stream);
+
+/*
  * Affinity normalisation + reference-tap insertion.
  * Replaces NLSPNModel._affinity_normalization (src/model/nlspnmodel.py:179-201)
  * followed by _aff_insert (:261-269).

@@ -53,6 +53,10 @@ SIGNATURES = {
     "nlspn_head_epilogue_x3": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "nlspn_head_epilogue_prologue_x3": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                              _i, _i, _i, _i, _i, _i, _i, _u, _vp]),
+    "nlspn_head_backward_pre": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "nlspn_head_dgrad_single": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "nlspn_head_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "nlspn_head_wgrad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "nlspn_propagate_normalized": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _u, _vp]),
     "nlspn_prop_step": (_i, [_i, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _i, _i, _u, _vp]),
     "nlspn_workspace_bytes": (_sz, [_i, _i, _i, _i]),
@@ -117,7 +121,9 @@ AB_OPTIONAL = frozenset({"nlspn_resident_status", "nlspn_resident_config", "nlsp
                          "nlspn_gconv_x3_pack_layout", "nlspn_gconv_x3",
                          "nlspn_gconv_wgrad_bf16x3_workspace_bytes", "nlspn_gconv_wgrad_bf16x3",
                          "nlspn_gconv_wgrad_narrow_covers", "nlspn_gconv_wgrad_narrow_workspace_bytes",
-                         "nlspn_gconv_wgrad_narrow"})
+                         "nlspn_gconv_wgrad_narrow",
+                         "nlspn_head_backward_pre", "nlspn_head_dgrad_single", "nlspn_head_wgrad_workspace_bytes",
+                         "nlspn_head_wgrad"})
 
 _lib = None
 

@@ -1,12 +1,13 @@
 // C ABI of the seam-2 and head entry points (see include/nlspn_prop.h): the modulated
 // deformable convolution forward and backward, the S2D pyramid, the head epilogue and its
 // weight packing, and the affinity normalisation's forward.  The DCN, S2D, packing and
-// normalisation kernels are instantiated here; the head kernels in nlspn_kern_heads.hip and
-// nlspn_kern_heads_x3.hip.
+// normalisation kernels are instantiated here; the head kernels in nlspn_kern_heads.hip,
+// nlspn_kern_heads_x3.hip and (the backward) nlspn_kern_heads_bwd.hip.
 #include "nlspn_host.h"
 #include "nlspn_affnorm.h"
 #include "nlspn_heads.h"
 #include "nlspn_heads_x3.h"
+#include "nlspn_heads_bwd.h"
 #include "nlspn_mdcn.h"
 #include "nlspn_s2d.h"
 
@@ -152,9 +153,119 @@ int launch_heads_x3(HeadsArgs &a, void *stream) {
                          "nlspn_head_epilogue_x3");
 }
 
+// ---- the head epilogue's backward (nlspn_heads_bwd.h)
+// The shape rules shared by its entries, in the forward's order and wording
+int check_head_bwd_shape(int B, int C, int H, int W, int nout) {
+    if (C < 16 || C % 16) return fail(NLSPN_EINVAL, "head backward: C=%d (multiple of 16)", C);
+    if (nout < 1) return fail(NLSPN_EINVAL, "head backward: nout=%d", nout);
+    if (nout > 158) return fail(NLSPN_EUNSUPPORTED, "head backward: nout=%d (at most 158)", nout);
+    return check_nonempty(B, H, W);
+}
+// one image of a source (C planes) and of gpre (nout + 2 planes) below 2 GiB; B H W in int
+int check_head_bwd_size(int B, int C, int H, int W, int nout) {
+    const long long HW = (long long)H * W, planes = C > nout + 2 ? C : nout + 2;
+    if (HW * planes * 4 > 0x7fffffffLL || (long long)B * HW > 0x7fffffffLL) return fail(NLSPN_EINVAL, "head backward: input too large");
+    return NLSPN_OK;
+}
+
+// out[rows][n1][T] = the sum over nsl slabs of ws[(i n1p + j) T + t], slices in order
+int head_reduce(const float *ws, float *out, int n0, int n1, int n1p, int T, long long slab, int nsl, hipStream_t st,
+                const char *what) {
+    float unit = 1.f;
+    void *rargs[] = {&ws, &out, &n0, &n1, &n1p, &T, &slab, &nsl, &unit};
+    return launch_kernel(reinterpret_cast<const void *>(&gwgrad_reduce_kernel), dim3(elementwise_grid((long long)n0 * n1 * T)),
+                         dim3(256), rargs, 0, st, what);
+}
+
 }  // namespace
 
 extern "C" {
+
+int nlspn_head_backward_pre(const float *g_off_aff, const float *g_pred_init, const float *g_conf,
+                            const float *pred_init, const float *conf, float *gpre, int B, int H, int W, int nout,
+                            void *stream) {
+    if (!gpre) return fail(NLSPN_EINVAL, "head backward: null pointer");
+    if ((g_pred_init == nullptr) != (pred_init == nullptr) || (g_conf == nullptr) != (conf == nullptr))
+        return fail(NLSPN_EINVAL, "head backward: a head's gradient and saved output must both be given or both NULL");
+    NLSPN_TRY(check_head_bwd_shape(B, 16, H, W, nout));
+    NLSPN_TRY(check_head_bwd_size(B, 16, H, W, nout));
+    HeadPreArgs a{g_off_aff, g_pred_init, g_conf, pred_init, conf, gpre, B, nout, (long long)H * W};
+    void *args[] = {&a};
+    return launch_kernel(reinterpret_cast<const void *>(&head_pre_kernel), dim3(elementwise_grid((long long)B * (nout + 2) * H * W)),
+                         dim3(256), args, 0, as_stream(stream), "nlspn_head_backward_pre");
+}
+
+int nlspn_head_dgrad_single(const float *gpre, const float *w_id, const float *w_cf, float *d_fd_id, float *d_fd_cf,
+                            int B, int C, int H, int W, int nout, void *stream) {
+    if (!gpre) return fail(NLSPN_EINVAL, "head backward: null pointer");
+    if ((w_id == nullptr) != (d_fd_id == nullptr) || (w_cf == nullptr) != (d_fd_cf == nullptr))
+        return fail(NLSPN_EINVAL, "head backward: a head's weight and data gradient must both be given or both NULL");
+    NLSPN_TRY(check_head_bwd_shape(B, C, H, W, nout));
+    NLSPN_TRY(check_head_bwd_size(B, C, H, W, nout));
+    if (!d_fd_id && !d_fd_cf) return NLSPN_OK;
+    HeadDgSingleArgs a{gpre, w_id, w_cf, d_fd_id, d_fd_cf, B, C, H, W, nout};
+    void *args[] = {&a};
+    return launch_kernel(reinterpret_cast<const void *>(&head_dgrad_single_kernel), dim3(elementwise_grid((long long)B * H * W)),
+                         dim3(256), args, 0, as_stream(stream), "nlspn_head_dgrad_single");
+}
+
+size_t nlspn_head_wgrad_workspace_bytes(int B, int C, int H, int W, int nout) {
+    if (check_head_bwd_shape(B, C, H, W, nout) || check_head_bwd_size(B, C, H, W, nout)) return 0;
+    const HbPlan pl = hb_plan(B, C, H, W, nout);
+    return pl.fits ? (size_t)pl.floats * sizeof(float) : 0;
+}
+
+int nlspn_head_wgrad(const float *gpre, const float *fe1, const float *fd_oa, const float *fd_id, const float *fd_cf,
+                     float *dw_oa, float *db_oa, float *dw_id, float *db_id, float *dw_cf, float *db_cf, void *workspace,
+                     int64_t workspace_bytes, int B, int C, int H, int W, int nout, void *stream) {
+    if (!gpre || !fe1 || !fd_oa || !dw_oa || !db_oa || !workspace) return fail(NLSPN_EINVAL, "head backward: null pointer");
+    if ((fd_id == nullptr) != (dw_id == nullptr) || (fd_id == nullptr) != (db_id == nullptr) ||
+        (fd_cf == nullptr) != (dw_cf == nullptr) || (fd_cf == nullptr) != (db_cf == nullptr))
+        return fail(NLSPN_EINVAL, "head backward: a head's source and weight / bias gradients must all be given or all NULL");
+    NLSPN_TRY(check_head_bwd_shape(B, C, H, W, nout));
+    const HbPlan pl = hb_plan(B, C, H, W, nout);
+    if (workspace_bytes < pl.floats * (long long)sizeof(float))
+        return fail(NLSPN_EINVAL, "head backward: workspace too small (%lld bytes, needs %lld)", (long long)workspace_bytes,
+                    pl.floats * (long long)sizeof(float));
+    NLSPN_TRY(check_head_bwd_size(B, C, H, W, nout));
+    if (!pl.fits) return fail(NLSPN_EINVAL, "head backward: input too large");
+    hipStream_t st = as_stream(stream);
+    float *ws = static_cast<float *>(workspace);
+    HwgradArgs a{gpre, fd_oa, fe1, fd_id, fd_cf, ws, ws + pl.vec_off, pl.R, C, B, H, W,
+                 pl.mtiles, pl.ntiles, pl.nsl, pl.bw, pl.nbands, pl.units, pl.ups, pl.nvs};
+    void *args[] = {&a};
+    const void *fn = reinterpret_cast<const void *>(&hwgrad_kernel);
+    NLSPN_TRY(set_lds_attr(fn, kHbLdsBytes));
+    NLSPN_TRY(launch_kernel(fn, dim3((unsigned)(pl.mtiles * pl.ntiles * pl.nsl)), dim3(kHbNTHR), args, (size_t)kHbLdsBytes, st,
+                            "nlspn_head_wgrad"));
+    if (fd_id || fd_cf)
+        NLSPN_TRY(launch_kernel(reinterpret_cast<const void *>(&hwgrad_single_kernel), dim3((unsigned)(2 * C * pl.nvs)), dim3(256),
+                                args, 0, st, "nlspn_head_wgrad single"));
+    // one slab feeds three destinations: rows < nout whole, the id / cf rows' fe1 halves (their
+    // fd_oa halves are padding); the id / cf decoder halves come from the one-row partials
+    const int Clp = pl.ntiles * kHbNT;
+    NLSPN_TRY(head_reduce(ws, dw_oa, nout, 2 * C, Clp, 9, pl.slab, pl.nsl, st, "nlspn_head_wgrad reduce"));
+    float *const dws[2] = {dw_id, dw_cf};
+    for (int k = 0; k < 2; ++k) {
+        if (!dws[k]) continue;
+        NLSPN_TRY(head_reduce(ws + ((long long)(nout + k) * Clp + C) * 9, dws[k] + (long long)C * 9, 1, C, Clp, 9, pl.slab, pl.nsl,
+                              st, "nlspn_head_wgrad reduce"));
+        NLSPN_TRY(head_reduce(a.vec + (long long)k * C * 9, dws[k], 1, C, C, 9, 2LL * C * 9, pl.nvs, st, "nlspn_head_wgrad reduce"));
+    }
+    // db: the per-row sums of gpre
+    {
+        int R = pl.R, nsb = pl.nsb, Bv = B;
+        long long HW = (long long)H * W;
+        float *part = ws + pl.bias_off;
+        void *pargs[] = {(void *)&gpre, &part, &R, &Bv, &HW, &nsb};
+        NLSPN_TRY(launch_kernel(reinterpret_cast<const void *>(&gbias_partial_kernel), dim3((unsigned)(R * nsb)), dim3(256), pargs,
+                                0, st, "nlspn_head_wgrad bias"));
+        NLSPN_TRY(head_reduce(part, db_oa, nout, 1, 1, 1, R, nsb, st, "nlspn_head_wgrad bias reduce"));
+        if (db_id) NLSPN_TRY(head_reduce(part + nout, db_id, 1, 1, 1, 1, R, nsb, st, "nlspn_head_wgrad bias reduce"));
+        if (db_cf) NLSPN_TRY(head_reduce(part + nout + 1, db_cf, 1, 1, 1, 1, R, nsb, st, "nlspn_head_wgrad bias reduce"));
+    }
+    return NLSPN_OK;
+}
 
 int nlspn_s2d_pyramid(int dtype, const void *dep, const float *w1, const float *b1, const float *w2,
                       const float *b2, void *out, void *pyr, int B, int H, int W, void *stream) {

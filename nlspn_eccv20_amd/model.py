@@ -254,6 +254,12 @@ class NLSPNModel(nn.Module):
         # DESIGN.md 3.7.1).  "fp32" (default) is the f32 kernel, bit for bit; ignored under
         # gradients and on the CPU, where the torch convolutions run
         self.head_precision = "fp32"
+        # native_head_train = True: under gradients (fe1 CUDA float32, not a DataParallel replica:
+        # native_gru_train's rule) the three head convolutions run as the fused f32 kernel with its
+        # HIP backward (heads.py _HeadFn, csrc/nlspn_heads_bwd.h): no cat copies,
+        # no MIOpen.  Always "fp32", whatever head_precision says (the split-bf16 kernels are
+        # inference only).  False (default): the torch modules, bit for bit; ignored at inference
+        self.native_head_train = False
         # GRU mode: encode_dep / encode_aff / ConvGRU / decode_aff as HIP convolutions (gru.py),
         # at inference and, with native_gru_train, under gradients (their HIP backward:
         # nlspn_gconv_bwd.h; off by default: slower than the tuned modules);
@@ -300,6 +306,16 @@ class NLSPNModel(nn.Module):
         if value not in HEAD_PRECISIONS:
             raise ValueError(f"head_precision must be 'fp32' or 'bf16x3', got {value!r}")
         object.__setattr__(self, "_head_precision", value)
+
+    @property
+    def native_head_train(self) -> bool:
+        return self._native_head_train
+
+    @native_head_train.setter
+    def native_head_train(self, value):
+        if not isinstance(value, bool):
+            raise ValueError(f"native_head_train must be a bool, got {value!r}")
+        object.__setattr__(self, "_native_head_train", value)
 
     @property
     def gru_wgrad_precision(self) -> str:
@@ -395,6 +411,12 @@ class NLSPNModel(nn.Module):
             return head_epilogue(fe1, off_aff_fd1, self.off_aff_dec0, id_fd1, self.id_dec0, cf_fd1,
                                  self.cf_dec0 if self.args.conf_prop else None, weights=self._head_cache(),
                                  precision=self.head_precision)
+        if (self.native_head_train and torch.is_grad_enabled() and fe1.is_cuda and fe1.dtype == torch.float32
+                and not getattr(self, "_is_replica", False)):
+            # training, opt-in: the same f32 kernel under autograd, its backward on the HIP kernels
+            return head_epilogue(fe1, off_aff_fd1, self.off_aff_dec0, id_fd1, self.id_dec0, cf_fd1,
+                                 self.cf_dec0 if self.args.conf_prop else None, weights=self._head_cache(),
+                                 precision="fp32", differentiable=True)
         pred_init = self.id_dec0(torch.cat((id_fd1, fe1), 1))
         off_aff = self.off_aff_dec0(torch.cat((off_aff_fd1, fe1), 1))
         confidence = None
