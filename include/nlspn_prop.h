@@ -727,6 +727,48 @@ int nlspn_gconv_x3(int layer, const void *x0, int c0, const void *x1, int c1, co
                    void *houts, int B, int Hi, int Wi, int cout, int ohs, int ows, int act, float in_div, int hc,
                    void *stream);
 
+/*
+ * Data gradients of the GRU-mode convolutions on the split-bf16 family, training, opt-in
+ * (csrc/nlspn_gconv_x3.h, the kGcEpiDact epilogue; NLSPNModel.gru_dgrad_precision = "bf16x3").
+ * nlspn_gconv_dgrad's launches (a forward launch of the adjoint layer kind with the derivative
+ * epilogue) with the gradient read as c8x2 and the adjoint weights packed split.  Numerics
+ * contract, beside the one above: per output element
+ *     dx = act'(ysave) * scale * sum (w_hi g_hi + w_hi g_lo + w_lo g_hi) (+ add),
+ * the sum in the MFMAs' f32 accumulators, the epilogue in f32 with nlspn_gconv_dgrad's
+ * arithmetic; a term is off by at most 2^-15 |w g| before accumulation rounding; nothing is
+ * clamped; no atomics and no waiting between workgroups: the same bits on every run.
+ * Presets (weights: nlspn_gconv_x3_dgrad_pack_layout; gru.py pack_adjoint_x3 / pack_adjoint_s1_x3):
+ *   NLSPN_GCX3_DG_T2       adjoint of a stride-2 conv, 64-channel co tile (NLSPN_GCX3_T2's tiling)
+ *   NLSPN_GCX3_DG_T2_C16   the same, 16-channel co tile (NLSPN_GCX3_T2_C16's tiling)
+ *   NLSPN_GCX3_DG_S2       adjoint of a stride-2 transposed conv (NLSPN_GCX3_S2's tiling)
+ *   NLSPN_GCX3_DG_S1       adjoint of a stride-1 conv (NLSPN_GCX3_GRU2's tile, plain epilogue)
+ * nlspn_gconv_x3_dgrad: nlspn_gconv_dgrad's arguments with gs the gradient (B, cg, Hg, Wg) as
+ * c8x2 and wpk bf16; ysave, add0, add1, dx0, dx1 stay f32 NCHW (add0 / add1 may alias dx0 / dx1).
+ * dxs (optional; needs split = cout): dx0's values split into a c8x2 tensor (B, ceil(cout/8), 2,
+ * Ho, Wo, 8), what the next data gradient of a chain reads.  Validation is nlspn_gconv_dgrad's
+ * (NLSPN_EINVAL: null pointers, a preset that is not NLSPN_GCX3_DG_*, split / second output
+ * mismatch, dxs with two outputs, an activation without ysave or with two outputs, an output
+ * size that does not belong to the gradient, a problem too large for 32-bit offsets);
+ * NLSPN_EUNSUPPORTED for what the family does not serve and nlspn_gconv_dgrad does: a
+ * stride-2-mode gradient stored cropped (Hg != 2 Ho or Wg != 2 Wo), a gradient of at most 16
+ * channels (cg <= 16, whatever cout: the problems with both channel counts <= 16 and, by
+ * measurement, the 2hc -> 16 decoder layer's adjoint), a grid no tile fits.  nlspn_gconv_x3_dgrad_covers answers 1 exactly for the
+ * shapes the entry serves (no device call, no error text).
+ * nlspn_gconv_x3_split: f32 (B, C, H, W) -> c8x2 (B, ceil(C/8), 2, H, W, 8), pad channels zero,
+ * every value split as the kernels' epilogues split it (bit-equal to gru.py to_c8x2): where a
+ * gradient enters a chain in f32.  x needs 4-byte alignment only, xs 16-byte.
+ */
+#define NLSPN_GCX3_DG_T2 80
+#define NLSPN_GCX3_DG_T2_C16 81
+#define NLSPN_GCX3_DG_S2 82
+#define NLSPN_GCX3_DG_S1 83
+int nlspn_gconv_x3_split(const float *x, void *xs, int B, int C, int H, int W, void *stream);
+int nlspn_gconv_x3_dgrad_covers(int layer, int cg, int cout, int Hg, int Wg, int Ho, int Wo);
+int nlspn_gconv_x3_dgrad(int layer, const void *gs, int cg, const void *wpk, const float *ysave, const float *add0,
+                         const float *add1, float *dx0, float *dx1, int split, void *dxs, int B, int Hg, int Wg,
+                         int cout, int Ho, int Wo, int act, float scale, void *stream);
+int nlspn_gconv_x3_dgrad_pack_layout(int layer, int *co_tile, int *cin_chunk, int *transposed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,11 @@ SIGNATURES = {
     "nlspn_gconv_x3_pack_layout": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "nlspn_gconv_x3": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i,
                             _i, ctypes.c_float, _i, _vp]),
+    "nlspn_gconv_x3_split": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "nlspn_gconv_x3_dgrad_covers": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "nlspn_gconv_x3_dgrad": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i,
+                                  ctypes.c_float, _vp]),
+    "nlspn_gconv_x3_dgrad_pack_layout": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
 }
 
 # Entry points an A/B build (NLSPN_LIB_PATH) of an earlier round may lack; any other
@@ -122,6 +127,8 @@ AB_OPTIONAL = frozenset({"nlspn_resident_status", "nlspn_resident_config", "nlsp
                          "nlspn_gconv_wgrad_bf16x3_workspace_bytes", "nlspn_gconv_wgrad_bf16x3",
                          "nlspn_gconv_wgrad_narrow_covers", "nlspn_gconv_wgrad_narrow_workspace_bytes",
                          "nlspn_gconv_wgrad_narrow",
+                         "nlspn_gconv_x3_split", "nlspn_gconv_x3_dgrad_covers", "nlspn_gconv_x3_dgrad",
+                         "nlspn_gconv_x3_dgrad_pack_layout",
                          "nlspn_head_backward_pre", "nlspn_head_dgrad_single", "nlspn_head_wgrad_workspace_bytes",
                          "nlspn_head_wgrad"})
 

@@ -25,6 +25,7 @@ extern template __global__ void gsmall16_kernel<16>(Gconv16Args, const float *);
 // defined in nlspn_kern_gconv_x3.hip
 #define NLSPN_GCX3_EXTERN(id, ...) extern template __global__ void gconvx3_kernel<__VA_ARGS__>(GconvX3Args);
 NLSPN_GCX3_CONFIGS(NLSPN_GCX3_EXTERN)
+NLSPN_GCX3_DG_CONFIGS(NLSPN_GCX3_EXTERN)
 extern template __global__ void gsmallx3_kernel<16>(GconvX3Args, const float *);
 // defined in nlspn_kern_gwgrad16.hip
 #define NLSPN_GW16_EXTERN(...) extern template __global__ void gwgrad16_kernel<__VA_ARGS__>(GwgradArgs);
@@ -84,6 +85,12 @@ bool gcx3_get(int layer, GcPreset &p) {
 #define NLSPN_GCX3_CASE(id, ...) \
     case id: p = gcx3_preset<__VA_ARGS__>(); return true;
         NLSPN_GCX3_CONFIGS(NLSPN_GCX3_CASE)
+        default: return false;
+    }
+}
+bool gcx3_dg_get(int layer, GcPreset &p) {
+    switch (layer) {
+        NLSPN_GCX3_DG_CONFIGS(NLSPN_GCX3_CASE)
         default: return false;
     }
 }
@@ -649,6 +656,96 @@ int nlspn_gconv_x3(int layer, const void *x0, int c0, const void *x1, int c1, co
     if (nwg > 0x7fffffffLL || (long long)std::max(a.nb0, a.nb1) * Hi * Wi * 16 > 0x7fffffffLL)
         return fail(NLSPN_EINVAL, "gconv_x3: problem too large");
     return gc_launch(p, a, nwg, stream, "nlspn_gconv_x3");
+}
+
+// ---------------------------------------------------------------- split-bf16 data gradients
+int nlspn_gconv_x3_split(const float *x, void *xs, int B, int C, int H, int W, void *stream) {
+    if (!x || !xs) return fail(NLSPN_EINVAL, "gconv_x3 split: null input or output");
+    if (B < 1 || C < 1 || H < 1 || W < 1) return fail(NLSPN_EINVAL, "gconv_x3 split: bad shape B=%d C=%d %dx%d", B, C, H, W);
+    Gx3SplitArgs a{};
+    a.x = x; a.xs = static_cast<__bf16 *>(xs); a.C = C; a.nb = (C + 7) / 8;
+    a.HW = (long long)H * W; a.n = (long long)B * a.nb * a.HW;
+    void *args[] = {&a};
+    return launch_kernel(reinterpret_cast<const void *>(&gcx3_split_kernel), dim3(elementwise_grid(a.n)), dim3(256), args, 0,
+                         as_stream(stream), "nlspn_gconv_x3_split");
+}
+
+int nlspn_gconv_x3_dgrad_pack_layout(int layer, int *co_tile, int *cin_chunk, int *transposed) {
+    GcPreset p;
+    if (!gcx3_dg_get(layer, p))
+        return fail(NLSPN_EINVAL, "gconv_x3 dgrad: preset %d is not a split-bf16 data-gradient preset (NLSPN_GCX3_DG_*)", layer);
+    return gc_pack_layout(&p, co_tile, cin_chunk, transposed);
+}
+
+}  // extern "C"
+namespace {
+// a data gradient's sizes against its preset's mode, as nlspn_gconv_dgrad accepts them
+bool gcx3_dg_oksize(int mode, int Hg, int Wg, int Ho, int Wo) {
+    return mode == kGcS1   ? (Ho == Hg && Wo == Wg)
+           : mode == kGcT2 ? (Ho <= 2 * Hg && Ho >= 2 * Hg - 1 && Wo <= 2 * Wg && Wo >= 2 * Wg - 1)
+                           : (Hg <= 2 * Ho && Wg <= 2 * Wo);
+}
+// what the family serves of those: null, or why not.  A stride-2-mode gradient stored cropped is
+// the f32 last decoder layer's alone.  A gradient of at most 16 channels is one 16-channel chunk:
+// nine k-steps under an epilogue that stores as much as the f32 kernel's, and it measured slower
+// than the f32 entry (the 2hc -> 16 decoder layer's adjoint at NYU B=8: 97.6 us with its split
+// launch against 52.3 us); with at most 16 output channels too it is mostly padding.
+// Both stay on nlspn_gconv_dgrad.
+const char *gcx3_dg_unserved(const GcPreset &p, int cg, int cout, int Hg, int Wg, int Ho, int Wo) {
+    if (p.mode == kGcS2 && (Hg != 2 * Ho || Wg != 2 * Wo)) return "a stride-2-mode gradient stored cropped";
+    if (cg <= 16) return "a gradient of at most 16 channels";
+    GcTiling t;
+    const bool tr = p.mode == kGcT2;
+    if (!nlspn::gc_tile(GcGeo{p.mode, p.wgco, p.npx, p.xr, p.xp}, tr ? Hg : Ho, tr ? Wg : Wo, t))
+        return "a grid no tile fits";
+    return nullptr;
+}
+}  // namespace
+extern "C" {
+
+int nlspn_gconv_x3_dgrad_covers(int layer, int cg, int cout, int Hg, int Wg, int Ho, int Wo) {
+    GcPreset p;
+    if (!gcx3_dg_get(layer, p) || cg < 1 || cout < 1 || Hg < 1 || Wg < 1 || Ho < 1 || Wo < 1) return 0;
+    return gcx3_dg_oksize(p.mode, Hg, Wg, Ho, Wo) && !gcx3_dg_unserved(p, cg, cout, Hg, Wg, Ho, Wo) ? 1 : 0;
+}
+
+int nlspn_gconv_x3_dgrad(int layer, const void *gs, int cg, const void *wpk, const float *ysave, const float *add0,
+                         const float *add1, float *dx0, float *dx1, int split, void *dxs, int B, int Hg, int Wg,
+                         int cout, int Ho, int Wo, int act, float scale, void *stream) {
+    GcPreset p;
+    if (!gcx3_dg_get(layer, p))
+        return fail(NLSPN_EINVAL, "gconv_x3 dgrad: preset %d is not a split-bf16 data-gradient preset (NLSPN_GCX3_DG_*)", layer);
+    if (!gs || !wpk || !dx0) return fail(NLSPN_EINVAL, "gconv_x3 dgrad: null gradient, weights or output");
+    if (B < 1 || Hg < 1 || Wg < 1 || cg < 1 || cout < 1 || Ho < 1 || Wo < 1)
+        return fail(NLSPN_EINVAL, "gconv_x3 dgrad: bad shape B=%d %dx%d cg=%d cout=%d out %dx%d", B, Hg, Wg, cg, cout, Ho, Wo);
+    if (split < 1 || split > cout || (split < cout) != (dx1 != nullptr) || (add1 && !dx1))
+        return fail(NLSPN_EINVAL, "gconv_x3 dgrad: cout mismatch: split %d of cout %d %s a second output", split, cout,
+                    dx1 ? "with" : "without");
+    if (dxs && split != cout) return fail(NLSPN_EINVAL, "gconv_x3 dgrad: the split copy needs one output tensor (split = cout)");
+    if (act < NLSPN_GC_ACT_NONE || act > NLSPN_GC_ACT_TANH || (act != NLSPN_GC_ACT_NONE && (!ysave || split != cout)))
+        return fail(NLSPN_EINVAL, "gconv_x3 dgrad: activation %d needs the saved output and one output tensor", act);
+    if (!gcx3_dg_oksize(p.mode, Hg, Wg, Ho, Wo))
+        return fail(NLSPN_EINVAL, "gconv_x3 dgrad: output %dx%d does not belong to gradient %dx%d", Ho, Wo, Hg, Wg);
+    if (const char *why = gcx3_dg_unserved(p, cg, cout, Hg, Wg, Ho, Wo))
+        return fail(NLSPN_EUNSUPPORTED, "gconv_x3 dgrad: %s is nlspn_gconv_dgrad's (nlspn_gconv_x3_dgrad_covers)", why);
+    GconvX3Args a{};
+    a.x0 = gs; a.w = wpk; a.y32 = dx0; a.y1 = dx1; a.ysplit = split; a.ys = static_cast<__bf16 *>(dxs);
+    a.ysave = ysave; a.add = add0; a.add1 = add1; a.scale = scale; a.act = act; a.in_div = 1.f;
+    a.c0 = cg; a.B = B; a.Hi = Hg; a.Wi = Wg;
+    if (p.mode == kGcT2) gc_out_size(kGcT2, Hg, Wg, a.Ho, a.Wo);
+    else { a.Ho = Ho; a.Wo = Wo; }
+    a.ohs = Ho; a.ows = Wo;
+    a.cout = cout;
+    const int ccb = p.cc / 4;  // the cell blocks of a chunk: a hi and a lo one per 8 channels
+    a.nb0 = 2 * ((cg + 7) / 8);
+    a.nbp = (a.nb0 + ccb - 1) / ccb * ccb;
+    a.co_tiles = (cout + p.wgco - 1) / p.wgco;
+    NLSPN_TRY(gc_tile(p, a, "gconv_x3 dgrad"));
+    const long long nwg = gc_wgs(p, a);
+    // (one image's cell blocks of the gradient within a 32-bit buffer descriptor)
+    if (nwg > 0x7fffffffLL || (long long)a.nb0 * Hg * Wg * 16 > 0x7fffffffLL)
+        return fail(NLSPN_EINVAL, "gconv_x3 dgrad: problem too large");
+    return gc_launch(p, a, nwg, stream, "nlspn_gconv_x3_dgrad");
 }
 
 }  // extern "C"

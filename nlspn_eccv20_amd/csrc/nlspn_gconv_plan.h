@@ -93,6 +93,16 @@ NLSPN_HD constexpr int gc16_lds_bytes(int mode, int wgco, int xr, int xp, int cc
     X(67, kGcT2, 2, 2, 2, 2, 6, 40, 4, kGcEpiAct)                  \
     X(68, kGcT2, 1, 2, 1, 4, 6, 80, 4, kGcEpiAct)
 
+// The split-bf16 data-gradient presets NLSPN_GCX3_DG_* (nlspn_gconv_x3_dgrad): the tiling of the
+// forward preset of the adjoint layer kind (80: of 67, 81: of 68, 82: of 64; 83: GRU2's tile, 66,
+// as a plain stride-1 convolution) with the kGcEpiDact epilogue.  Instantiated in
+// nlspn_kern_gconv_x3_dg.hip.
+#define NLSPN_GCX3_DG_CONFIGS(X)                                   \
+    X(80, kGcT2, 2, 2, 2, 2, 6, 40, 4, kGcEpiDact)                 \
+    X(81, kGcT2, 1, 2, 1, 4, 6, 80, 4, kGcEpiDact)                 \
+    X(82, kGcS2, 2, 2, 2, 2, 12, 40, 4, kGcEpiDact)                \
+    X(83, kGcS1, 2, 2, 2, 2, 6, 40, 4, kGcEpiDact)
+
 // The LDS bytes of a split-bf16 preset: two stages of a chunk's weights [CCB][taps][WGCO] and
 // window [CCB][XR][XP] in 16-byte cells, each region rounded up to whole LDS-DMA rounds of the
 // workgroup.  A hi and a lo cell per eight channels: a 16-channel chunk (CCB 4) has the bytes of
@@ -108,6 +118,7 @@ NLSPN_HD constexpr int gcx3_lds_bytes(int mode, int wgco, int xr, int xp, int cc
 #define NLSPN_GCX3_BUDGET(id, MODE, WM, WN, WGM, WGN, XR, XP, CCB, EPI) \
     static_assert(gcx3_lds_bytes(MODE, 16 * WM * WGM, XR, XP, CCB) <= kGcX3LdsBudget, "split-bf16 preset " #id ": LDS budget");
 NLSPN_GCX3_CONFIGS(NLSPN_GCX3_BUDGET)
+NLSPN_GCX3_DG_CONFIGS(NLSPN_GCX3_BUDGET)
 #undef NLSPN_GCX3_BUDGET
 static_assert(gcx3_lds_bytes(kGcS1, 64, 6, 40, 8) > kGcX3LdsBudget, "a 32-channel chunk does not fit the GRU presets");
 

@@ -3,6 +3,13 @@
 // layers of nlspn_gconv.h as gconv16_kernel's implicit GEMM over (channel, tap), every f32
 // operand carried as two bf16 parts.  The f32 and f16 families are untouched.
 //
+// Under gradients, opt-in as well (NLSPNModel.gru_dgrad_precision = "bf16x3"), the same body
+// computes the data gradients: a forward launch of the adjoint layer kind (nlspn_gconv_bwd.h) on
+// the gradient as c8x2 and the adjoint weights packed split, with the f32 family's derivative
+// epilogue (kGcEpiDact; presets NLSPN_GCX3_DG_CONFIGS, entry nlspn_gconv_x3_dgrad).  The MFMA
+// loop, the staging and the fragment reads are the forward's; gcx3_split_kernel brings an f32
+// NCHW gradient into the layout where it enters a chain.
+//
 // Numerics contract (include/nlspn_prop.h):
 //   - Every MFMA operand value a (f32) is the pair hi = rne_bf16(a), lo = rne_bf16(a - hi), the
 //     subtraction in f32.  Weights are split once, when packed (gru.py pack_conv_x3 /
@@ -76,6 +83,14 @@ struct GconvX3Args {
     int act;
     float in_div;          // the VALU kernel only
     int hc;
+    // kGcEpiDact (nlspn_gconv_x3_dgrad; the other epilogues read none of these): y32 (channels
+    // [0, ysplit)) and y1 (channels [ysplit, cout)) = act'(ysave) * scale * sum (+ add / add1, laid
+    // out as y32 / y1; they may be y32 / y1 themselves), all f32 NCHW as GconvArgs'; x0 is the
+    // gradient as c8x2, bias is not read; ys (optional, ysplit = cout): the same value split
+    const float *ysave, *add, *add1;
+    float *y1;
+    int ysplit;
+    float scale;
 };
 
 template <int MODE, int WM, int WN, int WGM, int WGN, int XR, int XP, int CCB, int EPI>
@@ -272,7 +287,10 @@ __device__ __forceinline__ void gconvx3_body(const GconvX3Args &a, gx3_bf8 *lds,
 #pragma unroll
     for (int m = 0; m < WM; ++m)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) bs[m][r] = a.bias[co0 + 16 * m + 4 * lg + r];  // (padded to the co tiles)
+        for (int r = 0; r < 4; ++r) {
+            if constexpr (EPI == kGcEpiDact) bs[m][r] = 0.f;  // (a gradient carries no bias)
+            else bs[m][r] = a.bias[co0 + 16 * m + 4 * lg + r];  // (padded to the co tiles)
+        }
     const int hc = a.hc;
     const int gate = EPI == kGcEpiGru1 ? (cot * WGCO) / hc : 0;  // GRU1: 0 z, 1 r, 2 qx (uniform per tile)
 #pragma unroll
@@ -299,6 +317,42 @@ __device__ __forceinline__ void gconvx3_body(const GconvX3Args &a, gx3_bf8 *lds,
                     if (a.act == kGcActRelu) u[r] = u[r] < 0.f ? 0.f : u[r];  // (NaN kept, as torch's ReLU)
                     else if (a.act == kGcActTanh) u[r] = tanhf(u[r]);
                     if (a.y32 && ok && cg + r < a.cout) a.y32[((long long)b * a.cout + cg + r) * HWs + pixs] = u[r];
+                }
+                if (a.ys && ok && cg < 8 * nbo) gcx3_store4(a.ys, b, nbo, cg, HWs, pixs, u, a.cout - cg);
+            }
+        } else if constexpr (EPI == kGcEpiDact) {
+            // the f32 family's arm (nlspn_gconv.h): no bias; the block's saved outputs and addends
+            // are loaded first (an addend that is the output itself is this lane's own element)
+            const long long pixs = ok ? (long long)oy * a.ows + ox : 0;
+            const long long HWs = (long long)a.ohs * a.ows;
+            const int nbo = (a.cout + 7) >> 3;
+            auto at = [&](const int co) __attribute__((always_inline)) {
+                return co < a.ysplit ? ((long long)b * a.ysplit + co) * HWs + pixs
+                                     : ((long long)b * (a.cout - a.ysplit) + (co - a.ysplit)) * HWs + pixs;
+            };
+            float yv[WM][4], av[WM][4];
+#pragma unroll
+            for (int m = 0; m < WM; ++m)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int co = co0 + 16 * m + 4 * lg + r;
+                    const bool st = ok && co < a.cout;
+                    const float *ad = co < a.ysplit ? a.add : a.add1;
+                    yv[m][r] = st && a.act != kGcActNone ? a.ysave[at(co)] : 0.f;
+                    av[m][r] = st && ad ? ad[at(co)] : 0.f;
+                }
+#pragma unroll
+            for (int m = 0; m < WM; ++m) {
+                const int cg = co0 + 16 * m + 4 * lg;
+                float u[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int co = cg + r;
+                    u[r] = acc[m][n][r] * a.scale;
+                    if (a.act == kGcActRelu) u[r] = yv[m][r] > 0.f ? u[r] : 0.f;
+                    else if (a.act == kGcActTanh) u[r] = u[r] * (1.f - yv[m][r] * yv[m][r]);
+                    if (co < a.ysplit ? a.add != nullptr : a.add1 != nullptr) u[r] += av[m][r];
+                    if (ok && co < a.cout) (co < a.ysplit ? a.y32 : a.y1)[at(co)] = u[r];
                 }
                 if (a.ys && ok && cg < 8 * nbo) gcx3_store4(a.ys, b, nbo, cg, HWs, pixs, u, a.cout - cg);
             }
@@ -438,6 +492,18 @@ __global__ void __launch_bounds__(kGsNT) gsmallx3_kernel(GconvX3Args a, const fl
     }
 }
 
-// (the instantiated configurations NLSPN_GCX3_CONFIGS: nlspn_gconv_plan.h)
+// f32 NCHW -> c8x2 (nlspn_gconv_x3_split; defined in nlspn_kern_gconv_x3_dg.hip): where a gradient
+// enters a chain of split-bf16 data gradients in f32.  A lane per cell: eight channels of one
+// pixel, split as gcx3_store4 splits them, a 16-byte hi and a 16-byte lo store.
+struct Gx3SplitArgs {
+    const float *x;  // (B, C, H, W)
+    __bf16 *xs;      // (B, nb, 2, H, W, 8)
+    int C, nb;
+    long long HW, n;  // n = B nb HW cells
+};
+__global__ void gcx3_split_kernel(Gx3SplitArgs a);
+
+// (the instantiated configurations: NLSPN_GCX3_CONFIGS, nlspn_kern_gconv_x3.hip; NLSPN_GCX3_DG_CONFIGS,
+// nlspn_kern_gconv_x3_dg.hip; both lists in nlspn_gconv_plan.h)
 
 }  // namespace nlspn

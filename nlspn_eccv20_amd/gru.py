@@ -65,6 +65,16 @@ counts are both <= 16 (1 / 9 -> 16 and 16 -> 8; ``nlspn_gconv_wgrad_narrow_cover
 streaming kernel (``nlspn_gconv_wgrad_narrow``, ``csrc/nlspn_gwnarrow.h``: exact f32 products,
 two launches per call, the bias gradient from the staged operand), whatever ``wgrad_precision``
 is; every other layer keeps its entry and its bits.  ``stats["wgrad_narrow"]`` counts its launches.
+
+Opt-in under gradients as well (``GruConvs.dgrad_precision = "bf16x3"``, set through
+``NLSPNModel.gru_dgrad_precision``): the data gradients ``nlspn_gconv_x3_dgrad_covers`` accepts (the
+wide layers' and both ConvGRU adjoints) run on the split-bf16 convolution kernels
+(``nlspn_gconv_x3_dgrad``: the forward family's body with the derivative epilogue) on adjoint
+weights packed split (``pack_adjoint_x3`` / ``pack_adjoint_s1_x3``, cached beside the f32 adjoint
+packs when the mode first needs them).  A gradient is brought into ``c8x2`` where it enters a chain
+in f32 (``nlspn_gconv_x3_split``) and handed on split from one data gradient to the next; every
+other launch of the backward is unchanged.  ``stats["dgrad_x3"]`` / ``stats["split_x3"]`` count
+the new launches, ``stats["dgrad"]`` keeps counting the f32 entry's.
 """
 from __future__ import annotations
 
@@ -77,7 +87,7 @@ import torch.nn as nn
 
 from . import _lib
 
-__all__ = ["GruConvs", "pack_adjoint", "pack_adjoint_s1", "unpack_conv", "unpack_convt", "to_c8", "from_c8",
+__all__ = ["GruConvs", "pack_adjoint", "pack_adjoint_s1", "pack_adjoint_x3", "pack_adjoint_s1_x3", "unpack_conv", "unpack_convt", "to_c8", "from_c8",
            "pack_conv16", "pack_convt16", "unpack_conv16", "unpack_convt16", "split_bf16", "to_c8x2", "from_c8x2",
            "pack_conv_x3", "pack_convt_x3", "unpack_conv_x3", "unpack_convt_x3", "GC_S2", "GC_S2_C16", "GC_GRU1", "GC_GRU2", "GC_T2", "GC_T2_C16", "GC_S2_SMALL"]
 
@@ -88,6 +98,8 @@ GC_DG_T2, GC_DG_T2_C16, GC_DG_S2, GC_DG_S2_C16, GC_DG_S1 = range(32, 37)
 GC16_S2, GC16_GRU1, GC16_GRU2, GC16_T2, GC16_T2_C16, GC16_S2_SMALL = range(48, 54)
 # the split-bf16 presets (NLSPN_GCX3_*, csrc/nlspn_gconv_x3.h)
 GCX3_S2, GCX3_GRU1, GCX3_GRU2, GCX3_T2, GCX3_T2_C16, GCX3_S2_SMALL = range(64, 70)
+# the split-bf16 data-gradient presets (NLSPN_GCX3_DG_*): the adjoint kind's x3 tiling, derivative epilogue
+GCX3_DG_T2, GCX3_DG_T2_C16, GCX3_DG_S2, GCX3_DG_S1 = range(80, 84)
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 # the transposed conv's taps per output phase (py, px), in the kernel's order
 # (nlspn_gconv.h gc_tap): ky = 1 (py = 0) or 0, 2 (py = 1); likewise kx
@@ -101,7 +113,8 @@ class _Family(typing.NamedTuple):
     the input channels in blocks of 8 innermost, [co_tile][cin_pad/8][tap][co][8]), and its
     presets by layer kind (s2_c16 / t2_c16: at most 16 output channels; small: the VALU kernel).
     ``split``: every f32 weight goes in as two bf16 parts, per 8 input channels a hi block then
-    a lo block ([co_tile][2 cin_pad / 8][tap][co][8]: the c8x2 layout's channel order)."""
+    a lo block ([co_tile][2 cin_pad / 8][tap][co][8]: the c8x2 layout's channel order).
+    ``dg_query`` / ``dg``: the pack-layout query of the family's data-gradient presets ``dg``."""
     query: str
     dtype: torch.dtype
     block: int
@@ -113,6 +126,8 @@ class _Family(typing.NamedTuple):
     gru1: int
     gru2: int
     split: bool = False
+    dg_query: str = ""
+    dg: tuple = ()
 
 
 _F32 = _Family("nlspn_gconv_pack_layout", torch.float32, 1, GC_S2, GC_S2_C16, GC_T2, GC_T2_C16, GC_S2_SMALL, GC_GRU1, GC_GRU2)
@@ -120,7 +135,8 @@ _F32 = _Family("nlspn_gconv_pack_layout", torch.float32, 1, GC_S2, GC_S2_C16, GC
 _F16 = _Family("nlspn_gconv16_pack_layout", torch.float16, 8, GC16_S2, GC16_S2, GC16_T2, GC16_T2_C16, GC16_S2_SMALL,
                GC16_GRU1, GC16_GRU2)
 _X3 = _Family("nlspn_gconv_x3_pack_layout", torch.bfloat16, 8, GCX3_S2, GCX3_S2, GCX3_T2, GCX3_T2_C16, GCX3_S2_SMALL,
-              GCX3_GRU1, GCX3_GRU2, split=True)
+              GCX3_GRU1, GCX3_GRU2, split=True, dg_query="nlspn_gconv_x3_dgrad_pack_layout",
+              dg=(GCX3_DG_T2, GCX3_DG_T2_C16, GCX3_DG_S2, GCX3_DG_S1))
 _TAPS = [[(ky, kx) for ky in range(3) for kx in range(3)]]  # a conv: one part, all nine taps
 
 
@@ -128,7 +144,7 @@ def _layout_of(fam, layer):
     """(output-channel tile, input-channel chunk, transposed) of a preset of family ``fam``."""
     lib = _lib.get()  # a query: no device, no launch
     co, cc, tr = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(getattr(lib, fam.query)(layer, ctypes.byref(co), ctypes.byref(cc), ctypes.byref(tr)))
+    _lib.check(getattr(lib, fam.dg_query if layer in fam.dg else fam.query)(layer, ctypes.byref(co), ctypes.byref(cc), ctypes.byref(tr)))
     return co.value, cc.value, bool(tr.value)
 
 
@@ -233,11 +249,12 @@ def _has_relu(seq):
 class _Layer:
     # conv: the module (its parameters receive the gradients); adj / dg: the adjoint-packed
     # weights and the data-gradient preset (training, GruConvs._pack_adjoints)
-    __slots__ = ("layer", "w", "b", "cin", "cout", "act", "conv", "adj", "dg")
+    # adjx / dgx: the same for the split-bf16 data gradients (GruConvs._pack_adjoints_x3), or None
+    __slots__ = ("layer", "w", "b", "cin", "cout", "act", "conv", "adj", "dg", "adjx", "dgx")
 
     def __init__(self, layer, w, b, cin, cout, act, conv=None):
         self.layer, self.w, self.b, self.cin, self.cout, self.act = layer, w, b, cin, cout, act
-        self.conv, self.adj, self.dg = conv, None, None
+        self.conv, self.adj, self.dg, self.adjx, self.dgx = conv, None, None, None, None
 
 
 def _make_layer(fam, conv, act, valu):
@@ -286,6 +303,21 @@ def pack_adjoint_s1(weight):
     """A stride-1 (Cout, Cin, 3, 3) conv's data gradient: the conv with the taps flipped and
     the channels transposed, packed for GC_DG_S1."""
     return pack_conv(weight.detach().transpose(0, 1).flip(2, 3), None, GC_DG_S1)[0]
+
+
+def pack_adjoint_x3(conv):
+    """pack_adjoint for the split-bf16 data gradients (nlspn_gconv_x3_dgrad): the same adjoint
+    tensor packed with pack_convt_x3 / pack_conv_x3 for the NLSPN_GCX3_DG_* preset of its kind
+    (one stride-2-mode preset for every width)."""
+    if isinstance(conv, nn.ConvTranspose2d):
+        return GCX3_DG_S2, pack_conv_x3(conv.weight, None, GCX3_DG_S2)[0]
+    dg = GCX3_DG_T2_C16 if conv.in_channels <= 16 else GCX3_DG_T2
+    return dg, pack_convt_x3(conv.weight, None, dg)[0]
+
+
+def pack_adjoint_s1_x3(weight):
+    """pack_adjoint_s1's tensor (taps flipped, channels transposed) packed split for GCX3_DG_S1."""
+    return pack_conv_x3(weight.detach().transpose(0, 1).flip(2, 3), None, GCX3_DG_S1)[0]
 
 
 # ---------------------------------------------------------------------- f16 operands (nlspn_gconv16.h)
@@ -367,12 +399,14 @@ class _ChainFn(torch.autograd.Function):
         if layers[-1].act != ACT_NONE:  # the chain's last activation (the layers below: in the dgrad epilogues)
             g = gc._act_backward(g, acts[-1], layers[-1].act)
         grads = []
+        gs = None  # g as c8x2, when a split-bf16 data gradient wrote it for the next one
         for i in reversed(range(len(layers))):
             L, xin = layers[i], acts[i]
             scale = 1.0 / ctx.in_div if i == 0 else 1.0
             grads[:0] = gc._wgrad(L, xin, g, scale)
             if i > 0 or ctx.needs_input_grad[4]:
-                g = gc._dgrad(L, g, xin, layers[i - 1].act if i > 0 else ACT_NONE, scale)
+                below = (layers[i - 1], acts[i - 1]) if i > 1 or (i == 1 and ctx.needs_input_grad[4]) else None
+                g, gs = gc._dgrad(L, g, xin, layers[i - 1].act if i > 0 else ACT_NONE, scale, gs, below)
             else:
                 g = None
         return (None, None, None, None, g, *grads)
@@ -408,18 +442,30 @@ class _GruFn(torch.autograd.Function):
         dhn = dhn.contiguous()
         duq, drh, dh, dx = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h), torch.empty_like(x)
         duzr = torch.empty((B, 2 * hc, H, W), device=dev, dtype=torch.float32)
+        cio = hc + x.shape[1]
+        # "bf16x3": both adjoints on nlspn_gconv_x3_dgrad, the gate stages' f32 outputs split on entry
+        x3 = gc._dgrad_x3() and "adj_q_x3" in P and all(
+            gc._covers(GCX3_DG_S1, c, cio, H, W, H, W) for c in (hc, 2 * hc))
         _lib.call("nlspn_gconv_gru_gates_backward", dev, 1, dhn, z, None, q, h, None, duq, duzr, None, 0, B, hc, H, W,
                   _lib.STREAM)
         # convq's adjoint: d(r h) and its share of dx
-        _lib.call("nlspn_gconv_dgrad", dev, GC_DG_S1, duq, hc, P["adj_q"], None, None, None, drh, dx, hc, B, H, W,
-                  hc + x.shape[1], H, W, ACT_NONE, 1.0, _lib.STREAM)
+        if x3:
+            _lib.call("nlspn_gconv_x3_dgrad", dev, GCX3_DG_S1, gc._split(duq), hc, P["adj_q_x3"], None, None, None, drh,
+                      dx, hc, None, B, H, W, cio, H, W, ACT_NONE, 1.0, _lib.STREAM)
+        else:
+            _lib.call("nlspn_gconv_dgrad", dev, GC_DG_S1, duq, hc, P["adj_q"], None, None, None, drh, dx, hc, B, H, W,
+                      cio, H, W, ACT_NONE, 1.0, _lib.STREAM)
         _lib.call("nlspn_gconv_gru_gates_backward", dev, 2, dhn, z, r, None, h, drh, None, duzr, dh, 0, B, hc, H, W,
                   _lib.STREAM)
         # [convz; convr]'s adjoint, added into dh and dx in place
-        _lib.call("nlspn_gconv_dgrad", dev, GC_DG_S1, duzr, 2 * hc, P["adj_zr"], None, dh, dx, dh, dx, hc, B, H, W,
-                  hc + x.shape[1], H, W, ACT_NONE, 1.0, _lib.STREAM)
+        if x3:
+            _lib.call("nlspn_gconv_x3_dgrad", dev, GCX3_DG_S1, gc._split(duzr), 2 * hc, P["adj_zr_x3"], None, dh, dx, dh,
+                      dx, hc, None, B, H, W, cio, H, W, ACT_NONE, 1.0, _lib.STREAM)
+        else:
+            _lib.call("nlspn_gconv_dgrad", dev, GC_DG_S1, duzr, 2 * hc, P["adj_zr"], None, dh, dx, dh, dx, hc, B, H, W,
+                      cio, H, W, ACT_NONE, 1.0, _lib.STREAM)
         gc.stats["gates_bwd"] += 2
-        gc.stats["dgrad"] += 2
+        gc.stats["dgrad_x3" if x3 else "dgrad"] += 2
         dwq, dbq = gc._wgrad_raw(1, duq, rh, x, False, 1.0)
         dwzr, dbzr = gc._wgrad_raw(1, duzr, h, x, False, 1.0)
         return None, None, dh, dx, dwzr[:hc], dbzr[:hc], dwzr[hc:], dbzr[hc:], dwq, dbq
@@ -439,6 +485,10 @@ class GruConvs:
         # True: the layers nlspn_gconv_wgrad_narrow_covers accepts (stride 2, both channel counts
         # <= 16) take nlspn_gconv_wgrad_narrow (csrc/nlspn_gwnarrow.h), whatever wgrad_precision is
         self.wgrad_narrow = False
+        # "bf16x3": the data gradients nlspn_gconv_x3_dgrad_covers accepts (the wide layers' and the
+        # ConvGRU's) on the split-bf16 convolution kernels (nlspn_gconv_x3_dgrad,
+        # csrc/nlspn_gconv_x3.h); "fp32" (default): nlspn_gconv_dgrad everywhere
+        self.dgrad_precision = "fp32"
         self.reset_stats()
 
     def reset_stats(self):
@@ -447,9 +497,11 @@ class GruConvs:
         counts ConvGRU cell forwards; ``fwd16`` the forward launches of the f16-operand family;
         ``wgrad_x3`` the weight / bias gradient launches of the ``"bf16x3"`` mode, counted as
         ``wgrad`` counts the f32 entry's; ``fwd_x3`` the forward launches of the split-bf16 family;
-        ``wgrad_narrow`` the launches of the narrow layers' streaming entry (two per call)."""
+        ``wgrad_narrow`` the launches of the narrow layers' streaming entry (two per call);
+        ``dgrad_x3`` the data-gradient launches of the ``"bf16x3"`` data-gradient mode (``dgrad``
+        keeps counting the f32 entry's) and ``split_x3`` its f32 -> c8x2 launches."""
         self.stats = {"fwd": 0, "dgrad": 0, "wgrad": 0, "gates_bwd": 0, "gru_fwd": 0, "fwd16": 0, "wgrad_x3": 0,
-                      "fwd_x3": 0, "wgrad_narrow": 0}
+                      "fwd_x3": 0, "wgrad_narrow": 0, "dgrad_x3": 0, "split_x3": 0}
 
     @staticmethod
     def supported(model) -> bool:
@@ -484,7 +536,24 @@ class GruConvs:
             packed["adj_q"] = pack_adjoint_s1(g.convq.weight)
             packed["adj_zr"] = pack_adjoint_s1(torch.cat([g.convz.weight, g.convr.weight], 0))
 
+    @staticmethod
+    def _pack_adjoints_x3(model, packed):
+        """The split-bf16 adjoint packs beside the f32 ones (same entry, same invalidation key)."""
+        with torch.no_grad():
+            for L in packed["dep"] + packed["aff"] + packed["dec"]:
+                L.dgx, L.adjx = pack_adjoint_x3(L.conv)
+            g = model.GRU
+            packed["adj_q_x3"] = pack_adjoint_s1_x3(g.convq.weight)
+            packed["adj_zr_x3"] = pack_adjoint_s1_x3(torch.cat([g.convz.weight, g.convr.weight], 0))
+
     def pack(self, model):
+        P = self._pack_f32(model)
+        # (packed when the mode first needs them: under gradients with dgrad_precision = "bf16x3")
+        if torch.is_grad_enabled() and self.dgrad_precision == "bf16x3" and "adj_q_x3" not in P:
+            self._pack_adjoints_x3(model, P)
+        return P
+
+    def _pack_f32(self, model):
         params = [p for m in (model.encode_dep, model.encode_aff, model.GRU, model.decode_aff) for p in m.parameters()]
         key = (params[0].device, tuple((p.data_ptr(), p._version) for p in params))
         e = self._entries.get(params[0].device)
@@ -713,6 +782,8 @@ class GruConvs:
         with torch.no_grad():
             L = _make_layer(_F32, conv, act, True)
             L.dg, L.adj = pack_adjoint(conv)
+            if self.dgrad_precision == "bf16x3":
+                L.dgx, L.adjx = pack_adjoint_x3(conv)
         return self._chain([L], x, in_div=in_div, crop=crop)
 
     def _act_backward(self, g, y, act):
@@ -722,15 +793,46 @@ class GruConvs:
         self.stats["dgrad"] += 1
         return out
 
-    def _dgrad(self, L, g, xin, act_below, scale):
-        """dL/d(pre-activation of the layer below) = act_below'(xin) * scale * adjoint(L)(g)."""
+    def _dgrad_x3(self):
+        """Whether the data gradients take the split-bf16 entry where it covers them."""
+        if self.dgrad_precision not in ("fp32", "bf16x3"):
+            raise ValueError(f"dgrad_precision must be 'fp32' or 'bf16x3', got {self.dgrad_precision!r}")
+        return self.dgrad_precision == "bf16x3"
+
+    @staticmethod
+    def _covers(dgx, cg, cout, Hg, Wg, Ho, Wo):
+        return bool(_lib.get().nlspn_gconv_x3_dgrad_covers(dgx, cg, cout, Hg, Wg, Ho, Wo))
+
+    def _split(self, g):
+        """An f32 NCHW gradient as c8x2 (nlspn_gconv_x3_split): where it enters a chain in f32."""
+        B, C, H, W = g.shape
+        gs = _MX3.empty(B, C, H, W, g.device)
+        _lib.call("nlspn_gconv_x3_split", g.device, g, gs, B, C, H, W, _lib.STREAM)
+        self.stats["split_x3"] += 1
+        return gs
+
+    def _dgrad(self, L, g, xin, act_below, scale, gs=None, below=None):
+        """dL/d(pre-activation of the layer below) = act_below'(xin) * scale * adjoint(L)(g), and
+        its c8x2 copy or None.  gs: g as c8x2 when the data gradient before wrote it; below: the
+        (layer, input) whose data gradient follows, or None: with dgrad_precision = "bf16x3" a
+        covered launch also writes the split copy when that next one is covered too."""
         B, cg, Hg, Wg = g.shape
         dx = torch.empty_like(xin)
         _, cout, Ho, Wo = xin.shape
-        _lib.call("nlspn_gconv_dgrad", g.device, L.dg, g, cg, L.adj, xin if act_below != ACT_NONE else None, None,
+        ysave = xin if act_below != ACT_NONE else None
+        if self._dgrad_x3() and L.dgx is not None and self._covers(L.dgx, cg, cout, Hg, Wg, Ho, Wo):
+            dxs = None
+            if below is not None and below[0].dgx is not None and self._covers(
+                    below[0].dgx, cout, below[1].shape[1], Ho, Wo, *below[1].shape[2:]):
+                dxs = _MX3.empty(B, cout, Ho, Wo, g.device)
+            _lib.call("nlspn_gconv_x3_dgrad", g.device, L.dgx, self._split(g) if gs is None else gs, cg, L.adjx, ysave,
+                      None, None, dx, None, cout, dxs, B, Hg, Wg, cout, Ho, Wo, act_below, scale, _lib.STREAM)
+            self.stats["dgrad_x3"] += 1
+            return dx, dxs
+        _lib.call("nlspn_gconv_dgrad", g.device, L.dg, g, cg, L.adj, ysave, None,
                   None, dx, None, cout, B, Hg, Wg, cout, Ho, Wo, act_below, scale, _lib.STREAM)
         self.stats["dgrad"] += 1
-        return dx
+        return dx, None
 
     def _wgrad(self, L, xin, g, scale):
         if isinstance(L.conv, nn.ConvTranspose2d):  # small = the input, large = the (cropped) output gradient

@@ -284,7 +284,13 @@ class NLSPNModel(nn.Module):
         # DESIGN.md 3.8.5), whatever gru_wgrad_precision is; every other launch is unchanged.  False
         # (default) is the path above, bit for bit; ignored at inference and without native_gru_train
         self.gru_wgrad_narrow = False
-        params = nn.ParameterList([p for p in self.parameters() if p.requires_grad])
+        # gru_dgrad_precision = "bf16x3": where the native training path runs (native_gru_train,
+        # gradients on), the data gradients of the wide layers and of the ConvGRU on the split-bf16
+        # convolution kernels (nlspn_gconv_x3_dgrad, csrc/nlspn_gconv_x3.h); the
+        # forward, the weight gradients' launches and the gate arithmetic are unchanged.  "fp32"
+        # (default) is the path above, bit for bit; ignored everywhere else
+        self.gru_dgrad_precision = "fp32"
+        params =nn.ParameterList([p for p in self.parameters() if p.requires_grad])
         self.param_groups = [{"params": params, "lr": args.lr}]
 
     @property
@@ -336,6 +342,16 @@ class NLSPNModel(nn.Module):
         if not isinstance(value, bool):
             raise ValueError(f"gru_wgrad_narrow must be a bool, got {value!r}")
         self._gru_convs.wgrad_narrow = value
+
+    @property
+    def gru_dgrad_precision(self) -> str:
+        return self._gru_convs.dgrad_precision
+
+    @gru_dgrad_precision.setter
+    def gru_dgrad_precision(self, value):
+        if value not in ("fp32", "bf16x3"):
+            raise ValueError(f"gru_dgrad_precision must be 'fp32' or 'bf16x3', got {value!r}")
+        self._gru_convs.dgrad_precision = value
 
     def _gru_fp16(self, x) -> bool:
         """The f16-operand convolutions run: asked for, gradients off, and the HIP path would run."""
