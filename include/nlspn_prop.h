@@ -306,7 +306,7 @@ int nlspn_plan_launch(nlspn_plan_t plan, void *stream);
 int nlspn_plan_destroy(nlspn_plan_t plan);
 
 /*
- * Backward of nlspn_propagate (float32 storage): what autograd computes through
+ * Backward of nlspn_propagate (float32 or float16 storage): what autograd computes through
  * src/model/nlspnmodel.py:323-381 with the DCNv2 backward for each of the T DCN
  * calls (modulated_deform_conv_cuda.cu:124-280; vision.cpp:10 ->
  * modulated_deform_conv.h:46-86).  Takes the forward's inputs and its saved
@@ -327,8 +327,24 @@ int nlspn_plan_destroy(nlspn_plan_t plan);
  * in its second pass.  So neither may overlap any input, pred_inter, aff_norm,
  * conf_eff, the incoming gradients or each other (beyond the packed (B, 3K, H, W)
  * layout above), and after a failed call their contents are undefined.
+ *
+ * dtype NLSPN_DTYPE_F16: every const void * operand (pred_init, dep, conf, aff_raw,
+ * off_raw, pred_inter, aff_norm, conf_eff, grad_pred, grad_pred_inter) points to
+ * halves and grad_pred_init, grad_conf, grad_aff_raw, grad_off_raw are written as
+ * halves; gamma and grad_gamma stay float.  All arithmetic and every accumulator are
+ * float32 (or the float path's fixed point) in the workspace; each half gradient
+ * element is the float32 value rounded once (to nearest even, overflow to inf).
+ * The gradient outputs are not used as scratch: the two-pass form keeps dL/d(output)
+ * in T float planes per item of the workspace, the one-pass form accumulates the
+ * offsets' gradient in 2K.  The workspace is then
+ * nlspn_backward_workspace_bytes_dtype() bytes: the float32 size plus
+ * 4 * B*H*W * (T if 3x3 and 2K < T <= 3K, else 2K) bytes.  The launch form (resident
+ * pass 1, step launches, one-pass) is chosen as for float32.
+ * nlspn_backward_workspace_bytes_dtype(NLSPN_DTYPE_F32, ...) equals
+ * nlspn_backward_workspace_bytes(); a bad argument or dtype gives 0.
  */
 size_t nlspn_backward_workspace_bytes(int B, int H, int W, int kh, int kw);
+size_t nlspn_backward_workspace_bytes_dtype(int dtype, int B, int H, int W, int kh, int kw, int T);
 int nlspn_propagate_backward(int dtype, const void *pred_init, const void *dep, const void *conf,
                              const void *aff_raw, int64_t aff_bstride,
                              const void *off_raw, int64_t off_bstride, const float *gamma,
@@ -341,7 +357,8 @@ int nlspn_propagate_backward(int dtype, const void *pred_init, const void *dep, 
                              unsigned flags, void *stream);
 
 /*
- * Backward of nlspn_prop_step (float32, raw offsets or the no-offset branch): what
+ * Backward of nlspn_prop_step (float32 or float16 storage, raw offsets or the no-offset
+ * branch): what
  * autograd computes through one loop iteration, src/model/nlspnmodel.py:350-361, with
  * the DCNv2 backward of its _propagate_once (modulated_deform_conv_cuda.cu:124-280).
  * Used by the ConvGRU mode, where every iteration has its own affinity (:365-373).
@@ -351,9 +368,14 @@ int nlspn_propagate_backward(int dtype, const void *pred_init, const void *dep, 
  * recomputes that tap as 1 - sum of the others, so chaining it into
  * nlspn_affinity_normalize_backward gives the reference's _aff_insert gradient) and
  * grad_off (2K planes per item, contiguous).  workspace:
- * nlspn_prop_step_backward_workspace_bytes() bytes.
+ * nlspn_prop_step_backward_workspace_bytes() bytes.  NLSPN_DTYPE_F16: operands and
+ * gradients are halves, each gradient element the float32 value rounded once; the
+ * workspace is nlspn_prop_step_backward_workspace_bytes_dtype() bytes
+ * (4 * B*H*W * (3K + 4): the float gradient planes before the rounding), which for
+ * NLSPN_DTYPE_F32 equals the function above; a bad argument or dtype gives 0.
  */
 size_t nlspn_prop_step_backward_workspace_bytes(int B, int H, int W);
+size_t nlspn_prop_step_backward_workspace_bytes_dtype(int dtype, int B, int H, int W, int kh, int kw);
 int nlspn_prop_step_backward(int dtype, const void *feat, const void *conf, const void *dep,
                              const void *aff, int64_t aff_bstride, const void *off_raw,
                              int64_t off_bstride, const void *grad_out, void *grad_feat,
@@ -366,6 +388,8 @@ int nlspn_prop_step_backward(int dtype, const void *feat, const void *conf, cons
  * per item, contiguous; writes grad_aff_raw (K planes per item, contiguous) and, for
  * TGASS, grad_gamma (1 float, summed in a fixed order; 0 for other kinds; may be
  * NULL).  workspace: nlspn_affinity_normalize_backward_workspace_bytes() bytes.
+ * NLSPN_DTYPE_F16: aff_raw, grad_aff and grad_aff_raw are halves (float32 arithmetic,
+ * one rounding per element); gamma, grad_gamma and the workspace are as for float32.
  */
 size_t nlspn_affinity_normalize_backward_workspace_bytes(int B, int K, int H, int W);
 int nlspn_affinity_normalize_backward(int dtype, const void *aff_raw, int64_t aff_bstride,

@@ -73,9 +73,11 @@ SIGNATURES = {
     "nlspn_time_prop_step": (_i, [_i, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp, _i, _i, _i, _i, _i, _u, _i,
                                   _vp, _fp, _fp]),
     "nlspn_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "nlspn_backward_workspace_bytes_dtype": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "nlspn_propagate_backward": (_i, [_i, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _u, _vp]),
     "nlspn_prop_step_backward_workspace_bytes": (_sz, [_i, _i, _i]),
+    "nlspn_prop_step_backward_workspace_bytes_dtype": (_sz, [_i, _i, _i, _i, _i, _i]),
     "nlspn_prop_step_backward": (_i, [_i, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _i, _i, _i, _i, _i, _u, _vp]),
     "nlspn_affinity_normalize_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
@@ -130,7 +132,8 @@ AB_OPTIONAL = frozenset({"nlspn_resident_status", "nlspn_resident_config", "nlsp
                          "nlspn_gconv_x3_split", "nlspn_gconv_x3_dgrad_covers", "nlspn_gconv_x3_dgrad",
                          "nlspn_gconv_x3_dgrad_pack_layout",
                          "nlspn_head_backward_pre", "nlspn_head_dgrad_single", "nlspn_head_wgrad_workspace_bytes",
-                         "nlspn_head_wgrad"})
+                         "nlspn_head_wgrad",
+                         "nlspn_backward_workspace_bytes_dtype", "nlspn_prop_step_backward_workspace_bytes_dtype"})
 
 _lib = None
 

@@ -1,4 +1,8 @@
-// Backward of the fused NLSPN propagation for gfx950 (CDNA4), fp32.
+// Backward of the fused NLSPN propagation for gfx950 (CDNA4): fp32 arithmetic over fp32 or
+// fp16 storage (the kernels' storage type S).  With fp16 storage the inputs, the saved tensors
+// and the upstream gradients are halves and every gradient but gamma's is written as a half,
+// rounded once; every accumulator (the dL/df planes, G, dL/dconf', the dL/dgamma partials, the
+// dL/dout store, the one-pass form's dL/doffset) is a float plane of the workspace.
 //
 // What the reference gets from autograd over nlspnmodel.py:323-381, with the
 // DCNv2 backward (src/model/deformconv/src/cuda/modulated_deform_conv_cuda.cu:124-280)
@@ -30,20 +34,21 @@
 
 namespace nlspn {
 
-struct BwdArgs {
-    const float *p_in;      // p_{t-1} (FIRST: pred_init)
-    const float *p_out;     // p_t (pred_inter[t-1])
-    const float *conf;      // FIRST: raw conf; else conf' (forward conf_out); null = conf_prop off
-    const float *conf_eff;  // conf' (forward conf_out) for the own-pixel product, or null
-    const float *dep;
-    const float *aff;       // normalised affinity (forward aff_out), (K+1) planes per item
-    const float *off;       // raw offsets (2K planes per item) or null (no-offset branch)
-    const float *g_pred;    // dL/dpred (used when t == T) or null
-    const float *g_inter;   // dL/dpred_inter[t-1] or null
+template <typename S>
+struct BwdArgsT {
+    const S *p_in;          // p_{t-1} (FIRST: pred_init)
+    const S *p_out;         // p_t (pred_inter[t-1])
+    const S *conf;          // FIRST: raw conf; else conf' (forward conf_out); null = conf_prop off
+    const S *conf_eff;      // conf' (forward conf_out) for the own-pixel product, or null
+    const S *dep;
+    const S *aff;           // normalised affinity (forward aff_out), (K+1) planes per item
+    const S *off;           // raw offsets (2K planes per item) or null (no-offset branch)
+    const S *g_pred;        // dL/dpred (used when t == T) or null
+    const S *g_inter;       // dL/dpred_inter[t-1] or null
     float *gf_read;         // dL/df_t   (scattered by step t+1); zeroed after use
     float *gf_write;        // dL/df_{t-1} (scattered here)
     float *g_aff;           // K planes per item: G_k = dL/daff_k - dL/daff_ref, accumulated
-    float *g_off;           // 2K planes per item (raw layout), accumulated = grad_off_raw
+    float *g_off;           // 2K planes per item (raw layout), accumulated (float storage: = grad_off_raw)
     float *g_conf;          // dL/dconf' plane, accumulated (null iff conf null)
     long long off_bs;
     int B, H, W, tiles_x, tiles_y;
@@ -52,17 +57,35 @@ struct BwdArgs {
                             //    K/2 untouched), 0: K planes (G form)
     unsigned flags;
     // FIRST only: affinity-normalisation backward fused in (per pixel, G final)
-    const float *aff_raw;   // raw head affinity, K planes per item at aff_raw_bs
+    const S *aff_raw;       // raw head affinity, K planes per item at aff_raw_bs
     long long aff_raw_bs;
     const float *gamma;
-    float *grad_aff_raw;    // K planes per item, batch stride gaff_bs (0: K*H*W)
+    S *grad_aff_raw;        // K planes per item, batch stride gaff_bs (0: K*H*W)
     long long gaff_bs, goff_bs;  // batch strides of grad_aff_raw / g_off in elements (0: contiguous)
     float *gamma_part;      // one partial dL/dgamma per workgroup (TGASS), or null
     int kind;
     // two-pass form (SPLIT): this iteration's dL/dout plane, written for bwd_coef_kernel
-    float *go_out;          // plane of item 0; item b at go_out + b * go_bs
+    float *go_out;          // plane of item 0 in the dL/dout store; item b at go_out + b * go_bs
     long long go_bs;
+    // FIRST, half storage: the finished dL/doffset goes here, rounded once (g_off stays the
+    // float accumulator); float storage: unused, g_off is the output
+    S *grad_off_raw;
+    long long groff_bs;     // its batch stride in elements (0: 2K*H*W)
 };
+using BwdArgs = BwdArgsT<float>;
+
+// One element of storage type S at byte offset vo + so of r, as a float / rounded once from one.
+template <typename S>
+__device__ __forceinline__ float blds(rsrc_t r, unsigned vo, unsigned so) {
+    float v[1];
+    BVec<S, 1>::load(r, vo, so, v);
+    return v[0];
+}
+template <typename S>
+__device__ __forceinline__ void bsts(rsrc_t r, unsigned vo, unsigned so, float x) {
+    const float v[1] = {x};
+    BVec<S, 1>::store(r, vo, so, v);
+}
 
 __device__ __forceinline__ float bld(rsrc_t r, unsigned vo, unsigned so) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0));
@@ -74,7 +97,7 @@ __device__ __forceinline__ void bst(rsrc_t r, unsigned vo, unsigned so, float v)
 // Bilinear corners of f_{t-1} at (hs, ws) (caller checked validity): from the LDS
 // window when the 2x2 footprint lies inside it, else from global memory with the
 // reference's per-corner checks (.cuh:24-54).
-template <bool FIRST, int WH, int WW>
+template <typename S, bool FIRST, int WH, int WW>
 __device__ __forceinline__ bool tap_corners(float hs, float ws, int wy0, int wx0, int H, int W, const float *win,
                                             rsrc_t rp, rsrc_t rc, rsrc_t rd, bool has_conf, bool preserve, bool clip,
                                             int &hl, int &wl, float (&v)[4]) {
@@ -86,12 +109,12 @@ __device__ __forceinline__ bool tap_corners(float hs, float ws, int wy0, int wx0
         v[0] = s[0]; v[1] = s[1]; v[2] = s[WW]; v[3] = s[WW + 1];
         return true;
     }
-    constexpr unsigned ES = 4;
+    constexpr unsigned ES = sizeof(S);
     const int r0 = hl * W, r1 = (hl + 1) * W;
-    v[0] = (hl >= 0 && wl >= 0) ? fetch_f<float, FIRST>(rp, rc, rd, has_conf, preserve, clip, (r0 + wl) * ES) : 0.f;
-    v[1] = (hl >= 0 && wl + 1 <= W - 1) ? fetch_f<float, FIRST>(rp, rc, rd, has_conf, preserve, clip, (r0 + wl + 1) * ES) : 0.f;
-    v[2] = (hl + 1 <= H - 1 && wl >= 0) ? fetch_f<float, FIRST>(rp, rc, rd, has_conf, preserve, clip, (r1 + wl) * ES) : 0.f;
-    v[3] = (hl + 1 <= H - 1 && wl + 1 <= W - 1) ? fetch_f<float, FIRST>(rp, rc, rd, has_conf, preserve, clip, (r1 + wl + 1) * ES) : 0.f;
+    v[0] = (hl >= 0 && wl >= 0) ? fetch_f<S, FIRST>(rp, rc, rd, has_conf, preserve, clip, (r0 + wl) * ES) : 0.f;
+    v[1] = (hl >= 0 && wl + 1 <= W - 1) ? fetch_f<S, FIRST>(rp, rc, rd, has_conf, preserve, clip, (r0 + wl + 1) * ES) : 0.f;
+    v[2] = (hl + 1 <= H - 1 && wl >= 0) ? fetch_f<S, FIRST>(rp, rc, rd, has_conf, preserve, clip, (r1 + wl) * ES) : 0.f;
+    v[3] = (hl + 1 <= H - 1 && wl + 1 <= W - 1) ? fetch_f<S, FIRST>(rp, rc, rd, has_conf, preserve, clip, (r1 + wl + 1) * ES) : 0.f;
     return false;
 }
 
@@ -153,9 +176,9 @@ __device__ __forceinline__ float aff_norm_backward(const float (&G)[K], const fl
 // scatters dL/df_{t-1}; the dL/daff and dL/doffset terms, which need f_{t-1} at every
 // tap, are computed for all T iterations afterwards by bwd_coef_kernel.  Without the
 // clamp's mask recomputation a SPLIT step stages no window and reads no accumulator.
-template <int KH, int KW, int TH, int TW, int RY, int RX, int SV, bool OFFSET, bool FIRST, int DIAG = 0,
+template <typename S, int KH, int KW, int TH, int TW, int RY, int RX, int SV, bool OFFSET, bool FIRST, int DIAG = 0,
           bool SPLIT = false>
-__global__ void __launch_bounds__(TH * TW) bwd_step_kernel(BwdArgs a) {
+__global__ void __launch_bounds__(TH * TW) bwd_step_kernel(BwdArgsT<S> a) {
     constexpr int NT = TH * TW;
     constexpr int KK = KH * KW, REF = KK / 2, K = KK - 1;
     constexpr int PH = (KH - 1) / 2, PW = (KW - 1) / 2;
@@ -166,7 +189,8 @@ __global__ void __launch_bounds__(TH * TW) bwd_step_kernel(BwdArgs a) {
     static_assert(SV == 1 || (OFFSET && RX % 4 == 0 && WW % 4 == 0), "vector staging alignment");
     constexpr int WV = WW / SV, NV = WH * WV, SIT = (NV + NT - 1) / NT;
     constexpr int NC = WH * WW, CIT = (NC + NT - 1) / NT;
-    constexpr unsigned ES = 4;
+    constexpr unsigned ES = sizeof(S);  // storage element; the accumulator planes are floats
+    constexpr bool F32 = sizeof(S) == 4;
     constexpr bool HOIST = K <= 8;
     constexpr int KO = OFFSET ? 2 * K : 1;
     static_assert(!SPLIT || OFFSET, "the two-pass form is for the offset branch");
@@ -188,7 +212,7 @@ __global__ void __launch_bounds__(TH * TW) bwd_step_kernel(BwdArgs a) {
     const bool preserve = (a.flags & kPreserve) != 0;
     const bool clip = (a.flags & kAlwaysClip) != 0;
     const bool last = a.last != 0;
-    const float *pbase = a.p_in + b * HW;
+    const S *pbase = a.p_in + b * HW;
     const rsrc_t rp = make_rsrc(pbase);
     const rsrc_t rc = make_rsrc(has_conf ? a.conf + b * HW : pbase);
     const rsrc_t rd = make_rsrc(preserve ? a.dep + b * HW : pbase);
@@ -196,7 +220,9 @@ __global__ void __launch_bounds__(TH * TW) bwd_step_kernel(BwdArgs a) {
     const int ly = threadIdx.x / TW, lx = threadIdx.x % TW;
     const int y = y0 + ly, x = x0 + lx;
     const bool active = (y < H) && (x < W);
-    const unsigned vpix = (active ? (unsigned)(y * W + x) : 0u) * ES, plane_bytes = (unsigned)HW * ES;
+    const unsigned pix = active ? (unsigned)(y * W + x) : 0u;
+    const unsigned vpix = pix * 4u, plane_bytes = (unsigned)HW * 4u;  // the float planes
+    const unsigned vps = pix * ES, plane_s = (unsigned)HW * ES;       // the storage-typed planes
 
     // ---- 1. all loads: window staging, tap planes, own pixel, accumulators
     const bool need_win = !SPLIT || clip;  // SPLIT: f_{t-1} only for the clamp's mask
@@ -213,31 +239,31 @@ __global__ void __launch_bounds__(TH * TW) bwd_step_kernel(BwdArgs a) {
         gy = gy < 0 ? 0 : (gy > H - 1 ? H - 1 : gy);
         gx = gx < 0 ? 0 : (gx > W - SV ? W - SV : gx);
         const unsigned q = (unsigned)(gy * W + gx) * ES;
-        BVec<float, SV>::load(rp, q, 0u, sp[it]);
-        if (has_conf) BVec<float, SV>::load(rc, q, 0u, sc[it]);
-        if (FIRST && preserve) BVec<float, SV>::load(rd, q, 0u, sd[FIRST ? it : 0]);
+        BVec<S, SV>::load(rp, q, 0u, sp[it]);
+        if (has_conf) BVec<S, SV>::load(rc, q, 0u, sc[it]);
+        if (FIRST && preserve) BVec<S, SV>::load(rd, q, 0u, sd[FIRST ? it : 0]);
     }
     const rsrc_t ra = make_rsrc(a.aff + b * (K + 1) * HW);
     const rsrc_t ro = make_rsrc(OFFSET ? a.off + b * a.off_bs : a.aff);
     float av[K], dh[OFFSET ? K : 1], dw[OFFSET ? K : 1];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        av[k] = bld(ra, vpix, (unsigned)(k < REF ? k : k + 1) * plane_bytes);
+        av[k] = blds<S>(ra, vps, (unsigned)(k < REF ? k : k + 1) * plane_s);
         if (OFFSET) {
-            dh[k] = bld(ro, vpix, (2u * k) * plane_bytes);
-            dw[k] = bld(ro, vpix, (2u * k + 1) * plane_bytes);
+            dh[k] = blds<S>(ro, vps, (2u * k) * plane_s);
+            dw[k] = blds<S>(ro, vps, (2u * k + 1) * plane_s);
         }
     }
     const rsrc_t rgc = make_rsrc(has_conf ? a.g_conf + b * HW : a.gf_read);
     const rsrc_t rgf = make_rsrc(a.gf_read + b * HW);
     float dv = 0.f, gfr = 0.f, pt = 0.f, ce = 1.f, gi = 0.f, gpr = 0.f, gcv = 0.f;
-    if (preserve) dv = bld(rd, vpix, 0u);
+    if (preserve) dv = blds<S>(rd, vps, 0u);
     if (!last) gfr = bld(rgf, vpix, 0u);
-    if (has_conf || (last && a.g_pred && !clip)) pt = bld(make_rsrc(a.p_out + b * HW), vpix, 0u);
-    if (has_conf) ce = bld(make_rsrc(a.conf_eff + b * HW), vpix, 0u);
+    if (has_conf || (last && a.g_pred && !clip)) pt = blds<S>(make_rsrc(a.p_out + b * HW), vps, 0u);
+    if (has_conf) ce = blds<S>(make_rsrc(a.conf_eff + b * HW), vps, 0u);
     if (has_conf && !last) gcv = bld(rgc, vpix, 0u);
-    if (a.g_inter) gi = bld(make_rsrc(a.g_inter + b * HW), vpix, 0u);
-    if (last && a.g_pred) gpr = bld(make_rsrc(a.g_pred + b * HW), vpix, 0u);
+    if (a.g_inter) gi = blds<S>(make_rsrc(a.g_inter + b * HW), vps, 0u);
+    if (last && a.g_pred) gpr = blds<S>(make_rsrc(a.g_pred + b * HW), vps, 0u);
     const bool gins = a.g_aff_ins != 0;
     const rsrc_t rga = make_rsrc(a.g_aff + b * (gins ? K + 1 : K) * HW);
     auto gplane = [&](int k) { return (unsigned)(gins && k >= REF ? k + 1 : k) * plane_bytes; };
@@ -315,7 +341,7 @@ __global__ void __launch_bounds__(TH * TW) bwd_step_kernel(BwdArgs a) {
                 if (hs > -1.f && ws > -1.f && hs < Hf && ws < Wf) {
                     int hl, wl;
                     float v[4];
-                    tap_corners<FIRST, WH, WW>(hs, ws, wy0, wx0, H, W, win, rp, rc, rd, has_conf, preserve, clip, hl, wl, v);
+                    tap_corners<S, FIRST, WH, WW>(hs, ws, wy0, wx0, H, W, win, rp, rc, rd, has_conf, preserve, clip, hl, wl, v);
                     const float lh = hs - (float)hl, lw = ws - (float)wl, hh = 1.f - lh, hw = 1.f - lw;
                     val[k] = (hh * hw * v[0] + hh * lw * v[1] + lh * hw * v[2] + lh * lw * v[3]);
                 }
@@ -406,7 +432,7 @@ __global__ void __launch_bounds__(TH * TW) bwd_step_kernel(BwdArgs a) {
                 if (hs > -1.f && ws > -1.f && hs < Hf && ws < Wf) {
                     int hl, wl;
                     float v[4];
-                    const bool inwin = tap_corners<FIRST, WH, WW>(hs, ws, wy0, wx0, H, W, win, rp, rc, rd, has_conf,
+                    const bool inwin = tap_corners<S, FIRST, WH, WW>(hs, ws, wy0, wx0, H, W, win, rp, rc, rd, has_conf,
                                                                   preserve, clip, hl, wl, v);
                     const float lh = hs - (float)hl, lw = ws - (float)wl, hh = 1.f - lh, hw = 1.f - lw;
                     const float w1 = hh * hw, w2 = hh * lw, w3 = lh * hw, w4 = lh * lw;
@@ -467,19 +493,26 @@ __global__ void __launch_bounds__(TH * TW) bwd_step_kernel(BwdArgs a) {
             }
         }
         if (OFFSET && !SPLIT && !(DIAG & 4)) {
+            if constexpr (FIRST && !F32) {
+                // half storage: the float accumulator is final, rounded once into grad_off_raw
+                const rsrc_t rout = make_rsrc(a.grad_off_raw + b * (a.groff_bs ? a.groff_bs : 2LL * K * HW));
 #pragma unroll
-            for (int k = 0; k < KO; ++k) bst(rgo, vpix, (unsigned)k * plane_bytes, cO[k]);
+                for (int k = 0; k < KO; ++k) bsts<S>(rout, vps, (unsigned)k * plane_s, cO[k]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < KO; ++k) bst(rgo, vpix, (unsigned)k * plane_bytes, cO[k]);
+            }
         }
         if (!SPLIT && FIRST) {
             // G is final for this pixel: normalisation backward -> grad_aff_raw, dL/dgamma partial
             const rsrc_t rar = make_rsrc(a.aff_raw + b * a.aff_raw_bs);
             float ar[K], ga[K];
 #pragma unroll
-            for (int k = 0; k < K; ++k) ar[k] = bld(rar, vpix, (unsigned)k * plane_bytes);
+            for (int k = 0; k < K; ++k) ar[k] = blds<S>(rar, vps, (unsigned)k * plane_s);
             gsum = aff_norm_backward<K>(cG, ar, *a.gamma, a.kind, ga);
             const rsrc_t rout = make_rsrc(a.grad_aff_raw + b * (a.gaff_bs ? a.gaff_bs : (long long)K * HW));
 #pragma unroll
-            for (int k = 0; k < K; ++k) bst(rout, vpix, (unsigned)k * plane_bytes, ga[k]);
+            for (int k = 0; k < K; ++k) bsts<S>(rout, vps, (unsigned)k * plane_s, ga[k]);
         } else if (!SPLIT && !(DIAG & 4)) {
 #pragma unroll
             for (int k = 0; k < K; ++k) bst(rga, vpix, gplane(k), cG[k]);
@@ -520,19 +553,32 @@ __global__ void __launch_bounds__(TH * TW) bwd_step_kernel(BwdArgs a) {
 // and offset planes are read once (the one-pass form re-reads them and read-modify-
 // writes 24 accumulator planes per iteration).  Step 1's normalisation backward and
 // dL/dgamma partial run at the end.
-// dL/dout_t is stored in the gradient outputs themselves (plane t-1 of grad_off_raw's
-// 2K planes, then of grad_aff_raw's K; T <= 3K): a pixel's dL/dout values are read only
-// by its own thread, before that thread writes its gradients over them.
+// With float storage dL/dout_t is stored in the gradient outputs themselves (plane t-1 of
+// grad_off_raw's 2K planes, then of grad_aff_raw's K; T <= 3K): a pixel's dL/dout values are
+// read only by its own thread, before that thread writes its gradients over them.  Half
+// outputs would round dL/dout, so with half storage the store is T float planes per item of
+// the workspace (BwdCoefArgsT's go_a / go_b describe either).
 #ifndef NLSPN_BWD_COEF_WAVES
 #define NLSPN_BWD_COEF_WAVES 1
 #endif
-struct BwdCoefArgs {
-    const float *pred_init, *pred_inter, *conf, *conf_eff, *dep, *aff, *off, *aff_raw, *gamma;
-    float *g_off, *grad_aff_raw, *gamma_part;
+template <typename S>
+struct BwdCoefArgsT {
+    const S *pred_init, *pred_inter, *conf, *conf_eff, *dep, *aff, *off, *aff_raw;
+    const float *gamma;
+    S *g_off, *grad_aff_raw;  // the outputs grad_off_raw (2K planes per item) and grad_aff_raw (K)
+    float *gamma_part;
     long long off_bs, aff_raw_bs, goff_bs, gaff_bs, N;  // batch strides resolved (non-zero)
     int B, H, W, tiles_x, tiles_y, T, kind;
     unsigned flags;
+    // The dL/dout store pass 1 filled, float planes: iteration t's plane is plane t-1 of go_a
+    // (item stride go_a_bs) while t-1 < go_na, else plane t-1-go_na of go_b (go_b_bs).  Float
+    // storage: the gradient outputs themselves (go_a = g_off, go_na = 2K, go_b = grad_aff_raw);
+    // half storage: T planes per item of the workspace (go_na = T), so dL/dout is never rounded.
+    float *go_a, *go_b;
+    long long go_a_bs, go_b_bs;
+    int go_na;
 };
+using BwdCoefArgs = BwdCoefArgsT<float>;
 
 // conf' (iteration-invariant) is staged into an LDS window once; iterations t >= 2 load only
 // p_{t-1} and form f = p * conf' from it (half the staging loads; measured within noise of
@@ -543,15 +589,15 @@ struct BwdCoefArgs {
 // -ffp-contract=off for the forward's exact IEEE sequence; the backward is checked to float
 // rounding, 1e-4 against the fp64 oracle and 1e-6 against the one-pass form): 0.4627 vs 0.4757
 // ms per C2 backward (profiles/r06/ab_bwd_pass2_fma.jsonl).
-template <int KH, int KW, int TH, int TW, int RY, int RX, int SV>
-__global__ void __launch_bounds__(TH * TW, NLSPN_BWD_COEF_WAVES) bwd_coef_kernel(BwdCoefArgs a) {
+template <typename S, int KH, int KW, int TH, int TW, int RY, int RX, int SV>
+__global__ void __launch_bounds__(TH * TW, NLSPN_BWD_COEF_WAVES) bwd_coef_kernel(BwdCoefArgsT<S> a) {
 #pragma clang fp contract(fast)
     constexpr int NT = TH * TW;
     constexpr int KK = KH * KW, REF = KK / 2, K = KK - 1;
     constexpr int PH = (KH - 1) / 2, PW = (KW - 1) / 2;
     constexpr int WH = TH + 2 * RY, WW = TW + 2 * RX;
     constexpr int WV = WW / SV, NV = WH * WV, SIT = (NV + NT - 1) / NT;
-    constexpr unsigned ES = 4;
+    constexpr unsigned ES = sizeof(S);
     static_assert(RY > PH && RX > PW, "window must cover the tap base grid");
     static_assert(SV == 1 || (RX % 4 == 0 && WW % 4 == 0), "vector staging alignment");
     __shared__ __attribute__((aligned(16))) float win[WH * WW];
@@ -573,7 +619,9 @@ __global__ void __launch_bounds__(TH * TW, NLSPN_BWD_COEF_WAVES) bwd_coef_kernel
     const int ly = threadIdx.x / TW, lx = threadIdx.x % TW;
     const int y = y0 + ly, x = x0 + lx;
     const bool active = (y < H) && (x < W);
-    const unsigned vpix = (active ? (unsigned)(y * W + x) : 0u) * ES, plane_bytes = (unsigned)HW * ES;
+    const unsigned pix = active ? (unsigned)(y * W + x) : 0u;
+    const unsigned vpix = pix * 4u, plane_bytes = (unsigned)HW * 4u;  // the dL/dout store's float planes
+    const unsigned vps = pix * ES, plane_s = (unsigned)HW * ES;       // the storage-typed planes
     const float Hf = (float)H, Wf = (float)W;
 
     const rsrc_t ra = make_rsrc(a.aff + b * (K + 1) * HW);
@@ -581,14 +629,16 @@ __global__ void __launch_bounds__(TH * TW, NLSPN_BWD_COEF_WAVES) bwd_coef_kernel
     float av[K], dh[K], dw[K], cG[K], cO[2 * K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        av[k] = bld(ra, vpix, (unsigned)(k < REF ? k : k + 1) * plane_bytes);
-        dh[k] = bld(ro, vpix, (2u * k) * plane_bytes);
-        dw[k] = bld(ro, vpix, (2u * k + 1) * plane_bytes);
+        av[k] = blds<S>(ra, vps, (unsigned)(k < REF ? k : k + 1) * plane_s);
+        dh[k] = blds<S>(ro, vps, (2u * k) * plane_s);
+        dw[k] = blds<S>(ro, vps, (2u * k + 1) * plane_s);
         cG[k] = 0.f;
         cO[2 * k] = cO[2 * k + 1] = 0.f;
     }
     const rsrc_t rgo = make_rsrc(a.g_off + b * a.goff_bs);
     const rsrc_t rgr = make_rsrc(a.grad_aff_raw + b * a.gaff_bs);
+    const rsrc_t rsa = make_rsrc(a.go_a + b * a.go_a_bs), rsb = make_rsrc(a.go_b + b * a.go_b_bs);
+    const int go_na = a.go_na;
     const bool cw = has_conf;  // (conf_prop off: f = p, nothing to keep)
     if (cw) {  // conf' over the window (zero outside the image), once
         const rsrc_t rc = make_rsrc(a.conf_eff + b * HW);
@@ -602,7 +652,7 @@ __global__ void __launch_bounds__(TH * TW, NLSPN_BWD_COEF_WAVES) bwd_coef_kernel
             gy = gy < 0 ? 0 : (gy > H - 1 ? H - 1 : gy);
             gx = gx < 0 ? 0 : (gx > W - SV ? W - SV : gx);
             float v[SV];
-            BVec<float, SV>::load(rc, (unsigned)(gy * W + gx) * ES, 0u, v);
+            BVec<S, SV>::load(rc, (unsigned)(gy * W + gx) * ES, 0u, v);
             if (i < NV) {
 #pragma unroll
                 for (int e = 0; e < SV; ++e) cwin[r * WW + c + e] = in ? v[e] : 0.f;
@@ -629,7 +679,7 @@ __global__ void __launch_bounds__(TH * TW, NLSPN_BWD_COEF_WAVES) bwd_coef_kernel
                 if (hs > -1.f && ws > -1.f && hs < Hf && ws < Wf) {
                     int hl, wl;
                     float v[4];
-                    tap_corners<FIRST, WH, WW>(hs, ws, wy0, wx0, H, W, win, rp, rc, rd, has_conf, preserve, clip, hl, wl, v);
+                    tap_corners<S, FIRST, WH, WW>(hs, ws, wy0, wx0, H, W, win, rp, rc, rd, has_conf, preserve, clip, hl, wl, v);
                     const float lh = hs - (float)hl, lw = ws - (float)wl, hh = 1.f - lh, hw = 1.f - lw;
                     const float w1 = hh * hw, w2 = hh * lw, w3 = lh * hw, w4 = lh * lw;
                     val = (w1 * v[0] + w2 * v[1] + w3 * v[2] + w4 * v[3]);
@@ -651,7 +701,7 @@ __global__ void __launch_bounds__(TH * TW, NLSPN_BWD_COEF_WAVES) bwd_coef_kernel
     };
     const auto iter = [&](auto first_c, int t) {
         constexpr bool FIRST = decltype(first_c)::value;
-        const float *pbase = FIRST ? a.pred_init + b * HW : a.pred_inter + (size_t)(t - 2) * a.N + b * HW;
+        const S *pbase = FIRST ? a.pred_init + b * HW : a.pred_inter + (size_t)(t - 2) * a.N + b * HW;
         const rsrc_t rp = make_rsrc(pbase);
         const rsrc_t rc = make_rsrc(has_conf ? (FIRST ? a.conf : a.conf_eff) + b * HW : pbase);
         const rsrc_t rd = make_rsrc(preserve ? a.dep + b * HW : pbase);
@@ -668,14 +718,14 @@ __global__ void __launch_bounds__(TH * TW, NLSPN_BWD_COEF_WAVES) bwd_coef_kernel
             gy = gy < 0 ? 0 : (gy > H - 1 ? H - 1 : gy);
             gx = gx < 0 ? 0 : (gx > W - SV ? W - SV : gx);
             const unsigned q = (unsigned)(gy * W + gx) * ES;
-            BVec<float, SV>::load(rp, q, 0u, sp[it]);
-            if (has_conf && (FIRST || !cw)) BVec<float, SV>::load(rc, q, 0u, sc[it]);
-            if (FIRST && preserve) BVec<float, SV>::load(rd, q, 0u, sd[FIRST ? it : 0]);
+            BVec<S, SV>::load(rp, q, 0u, sp[it]);
+            if (has_conf && (FIRST || !cw)) BVec<S, SV>::load(rc, q, 0u, sc[it]);
+            if (FIRST && preserve) BVec<S, SV>::load(rd, q, 0u, sd[FIRST ? it : 0]);
         }
         // this iteration's dL/dout at the own pixel (plane t-1 of the dL/dout store)
         const int j = t - 1;
-        const float go = active ? (j < 2 * K ? bld(rgo, vpix, (unsigned)j * plane_bytes)
-                                             : bld(rgr, vpix, (unsigned)(j - 2 * K) * plane_bytes))
+        const float go = active ? (j < go_na ? bld(rsa, vpix, (unsigned)j * plane_bytes)
+                                             : bld(rsb, vpix, (unsigned)(j - go_na) * plane_bytes))
                                 : 0.f;
 #pragma unroll
         for (int it = 0; it < SIT; ++it) {
@@ -708,14 +758,14 @@ __global__ void __launch_bounds__(TH * TW, NLSPN_BWD_COEF_WAVES) bwd_coef_kernel
     float gsum = 0.f;
     if (active) {
 #pragma unroll
-        for (int k = 0; k < 2 * K; ++k) bst(rgo, vpix, (unsigned)k * plane_bytes, cO[k]);
+        for (int k = 0; k < 2 * K; ++k) bsts<S>(rgo, vps, (unsigned)k * plane_s, cO[k]);
         const rsrc_t rar = make_rsrc(a.aff_raw + b * a.aff_raw_bs);
         float ar[K], ga[K];
 #pragma unroll
-        for (int k = 0; k < K; ++k) ar[k] = bld(rar, vpix, (unsigned)k * plane_bytes);
+        for (int k = 0; k < K; ++k) ar[k] = blds<S>(rar, vps, (unsigned)k * plane_s);
         gsum = aff_norm_backward<K>(cG, ar, *a.gamma, a.kind, ga);
 #pragma unroll
-        for (int k = 0; k < K; ++k) bst(rgr, vpix, (unsigned)k * plane_bytes, ga[k]);
+        for (int k = 0; k < K; ++k) bsts<S>(rgr, vps, (unsigned)k * plane_s, ga[k]);
     }
     if (a.gamma_part) {
         for (int o = 32; o > 0; o >>= 1) gsum += __shfl_down(gsum, o, 64);
@@ -734,24 +784,25 @@ __global__ void __launch_bounds__(TH * TW, NLSPN_BWD_COEF_WAVES) bwd_coef_kernel
 //   f_0 = p_0 * conf', p_0 = clamp(blend(pred_init)) (nlspnmodel.py:341-348, :351),
 //   conf' = (1-m) conf + m (:333-334) -> grad_pred_init, grad_conf;
 // workgroup 0 also sums step 1's per-workgroup dL/dgamma partials in a fixed order.
+template <typename S>
 __global__ void __launch_bounds__(256) bwd_final_kernel(
-    const float *pred_init, const float *dep, const float *conf, const float *conf_eff, const float *gf0,
-    const float *g_conf_acc, float *grad_pred_init, float *grad_conf, long long N, unsigned flags,
+    const S *pred_init, const S *dep, const S *conf, const S *conf_eff, const float *gf0,
+    const float *g_conf_acc, S *grad_pred_init, S *grad_conf, long long N, unsigned flags,
     const float *gamma_part, int n_part, float *grad_gamma) {
     const bool preserve = (flags & kPreserve) != 0, clip = (flags & kAlwaysClip) != 0;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
-        const float d = preserve ? dep[i] : 0.f;
+        const float d = preserve ? ld<S>(dep + i) : 0.f;
         const float m = d > 0.f ? 1.f : 0.f;
-        float pre = pred_init[i];
+        float pre = ld<S>(pred_init + i);
         if (preserve) pre = (1.0f - m) * pre + m * d;
         const float p0 = clip ? clamp0(pre) : pre;
         const float gfi = gf0[i];
-        float g = conf ? gfi * conf_eff[i] : gfi;
+        float g = conf ? gfi * ld<S>(conf_eff + i) : gfi;
         if (clip && !(pre >= 0.f)) g = 0.f;
-        grad_pred_init[i] = preserve ? (1.0f - m) * g : g;
+        st<S>(grad_pred_init + i, preserve ? (1.0f - m) * g : g);
         if (conf) {
             const float gc = g_conf_acc[i] + gfi * p0;
-            grad_conf[i] = preserve ? (1.0f - m) * gc : gc;
+            st<S>(grad_conf + i, preserve ? (1.0f - m) * gc : gc);
         }
     }
     if (grad_gamma && blockIdx.x == 0) {
@@ -769,25 +820,41 @@ __global__ void __launch_bounds__(256) bwd_final_kernel(
 // one prop_step (nlspnmodel.py:350-361): grad_feat = dL/df * conf, grad_conf =
 // dL/df * feat, and tap K/2 of the (K+1)-plane affinity gradient = 0 (the kernels
 // recompute that tap as 1 - sum of the others, so it does not enter the output).
-__global__ void __launch_bounds__(256) bwd_step_io_kernel(const float *feat, const float *conf, const float *gf,
-                                                           float *grad_feat, float *grad_conf, float *grad_aff,
-                                                           long long HW, int B, int K) {
+// Half storage: the step wrote its affinity and offset gradients as float planes of the
+// workspace (acc_aff, acc_off, the outputs' layouts); they are rounded once here.
+template <typename S>
+__global__ void __launch_bounds__(256) bwd_step_io_kernel(const S *feat, const S *conf, const float *gf,
+                                                           S *grad_feat, S *grad_conf, S *grad_aff,
+                                                           long long HW, int B, int K, const float *acc_aff,
+                                                           const float *acc_off, S *grad_off) {
     const long long N = (long long)B * HW;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
         const float g = gf[i];
-        grad_feat[i] = conf ? g * conf[i] : g;
-        if (conf) grad_conf[i] = g * feat[i];
+        st<S>(grad_feat + i, conf ? g * ld<S>(conf + i) : g);
+        if (conf) st<S>(grad_conf + i, g * ld<S>(feat + i));
         const long long b = i / HW, q = i - b * HW;
-        grad_aff[(b * (K + 1) + K / 2) * HW + q] = 0.f;
+        st<S>(grad_aff + (b * (K + 1) + K / 2) * HW + q, 0.f);
+        if (acc_aff) {
+            for (int k = 0; k <= K; ++k) {
+                const long long e = (b * (K + 1) + k) * HW + q;
+                if (k != K / 2) st<S>(grad_aff + e, acc_aff[e]);
+            }
+        }
+        if (acc_off) {
+            for (int k = 0; k < 2 * K; ++k) {
+                const long long e = (b * 2 * K + k) * HW + q;
+                st<S>(grad_off + e, acc_off[e]);
+            }
+        }
     }
 }
 
 // Backward of nlspn_affinity_normalize (_affinity_normalization + _aff_insert,
 // nlspnmodel.py:179-201, :261-269) for a (K+1)-plane gradient of its output:
 // G_k = g[k] - g[K/2], then aff_norm_backward; one dL/dgamma partial per workgroup.
-template <int K>
-__global__ void __launch_bounds__(256) affnorm_bwd_kernel(const float *aff_raw, long long aff_bs, const float *gamma_p,
-                                                          const float *grad_aff, float *grad_aff_raw,
+template <typename S, int K>
+__global__ void __launch_bounds__(256) affnorm_bwd_kernel(const S *aff_raw, long long aff_bs, const float *gamma_p,
+                                                          const S *grad_aff, S *grad_aff_raw,
                                                           float *gamma_part, long long HW, int B, int kind) {
     constexpr int REF = K / 2;
     const float gamma = *gamma_p;
@@ -795,17 +862,17 @@ __global__ void __launch_bounds__(256) affnorm_bwd_kernel(const float *aff_raw, 
     float gsum = 0.f;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
         const long long b = i / HW, q = i - b * HW;
-        const float *gin = grad_aff + b * (K + 1) * HW + q;
-        const float gref = gin[REF * HW];
+        const S *gin = grad_aff + b * (K + 1) * HW + q;
+        const float gref = ld<S>(gin + REF * HW);
         float G[K], ar[K], ga[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            G[k] = gin[(k < REF ? k : k + 1) * HW] - gref;
-            ar[k] = aff_raw[b * aff_bs + k * HW + q];
+            G[k] = ld<S>(gin + (k < REF ? k : k + 1) * HW) - gref;
+            ar[k] = ld<S>(aff_raw + b * aff_bs + k * HW + q);
         }
         gsum += aff_norm_backward<K>(G, ar, gamma, kind, ga);
 #pragma unroll
-        for (int k = 0; k < K; ++k) grad_aff_raw[(b * K + k) * HW + q] = ga[k];
+        for (int k = 0; k < K; ++k) st<S>(grad_aff_raw + (b * K + k) * HW + q, ga[k]);
     }
     if (gamma_part) {
         __shared__ float red[4];

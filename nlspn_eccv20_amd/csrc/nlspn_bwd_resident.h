@@ -56,18 +56,20 @@ constexpr unsigned kBrSpinLimit = 1u << 22;
 // then one adjacency row (kBrMaskWords) per part.  Zeroed by the host before each launch.
 constexpr size_t kBrSyncWords = (size_t)kBrLine * (1 + kBrMaxParts) + (size_t)kBrMaxParts * kBrMaskWords;
 
-struct BwdResArgs {
-    const float *pred_inter;  // T planes of N: plane t-1 = p_t
-    const float *conf_eff;    // conf' (forward conf_out), or null (conf_prop off)
-    const float *dep;         // null unless preserve_input
-    const float *aff;         // normalised affinity, (K+1) planes per item
-    const float *off;         // raw offsets, 2K planes per item at off_bs
-    const float *g_pred;      // dL/dpred or null
-    const float *g_inter;     // dL/dpred_inter, T planes of N, or null
+template <typename S>
+struct BwdResArgsT {
+    const S *pred_inter;      // T planes of N: plane t-1 = p_t
+    const S *conf_eff;        // conf' (forward conf_out), or null (conf_prop off)
+    const S *dep;             // null unless preserve_input
+    const S *aff;             // normalised affinity, (K+1) planes per item
+    const S *off;             // raw offsets, 2K planes per item at off_bs
+    const S *g_pred;          // dL/dpred or null
+    const S *g_inter;         // dL/dpred_inter, T planes of N, or null
     float *gf;                // two planes of N: dL/df ping-pong, zero on entry
     float *g_conf;            // dL/dconf' (the final kernel's accumulator plane), or null
-    float *g_off, *g_aff;     // dL/dout_t goes to plane t-1 of g_off (t-1 < 2K), else of g_aff
-    long long goff_bs, gaff_bs, off_bs, N;
+    float *go_a, *go_b;       // the dL/dout store (BwdCoefArgsT): dL/dout_t goes to plane t-1 of
+    int go_na;                // go_a (t-1 < go_na), else to plane t-1-go_na of go_b
+    long long go_a_bs, go_b_bs, off_bs, N;
     unsigned *sync;           // kBrSyncWords, zero on entry
     unsigned *status;         // host-mapped sticky abort word of the device, or null
     int H, W, T;               // (the whole batch in one launch)
@@ -78,6 +80,7 @@ struct BwdResArgs {
                               // scatter, 2 no halo flush, 4 no waits, 8 no exchange read, 16 part 0
                               // aborts at its first wait (the abort path's test)
 };
+using BwdResArgs = BwdResArgsT<float>;
 
 __device__ __forceinline__ unsigned br_load(const unsigned *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -101,8 +104,10 @@ __device__ __forceinline__ bool br_wait(unsigned *sync, unsigned *status, const 
 // (Two 512-thread parts per CU, each with half the pixels, so that one part's waits overlap the
 // other's scatter, measured no faster: C2 0.4566 vs 0.4536 ms per backward,
 // profiles/r06/ab_bwd_two_parts_per_cu_*_rejected.json.)
-template <int PX>
-__global__ void __launch_bounds__(kBrNT, 1) bwd_res_kernel(BwdResArgs a) {
+// S: the storage type of the inputs (float or __half); everything the part keeps, exchanges
+// and writes (the dL/dout store, dL/dconf', the dL/df planes) is float either way.
+template <typename S, int PX>
+__global__ void __launch_bounds__(kBrNT, 1) bwd_res_kernel(BwdResArgsT<S> a) {
     constexpr int K = 8, REF = 4, NT = kBrNT, R = kBrR;
     extern __shared__ __attribute__((aligned(16))) unsigned long long gacc[];  // WH x WW window, then avl
     float *avl = reinterpret_cast<float *>(gacc + ((a.WH * a.WW + 1) & ~1));  // K affinities per pixel (index i), 32 B each
@@ -137,7 +142,8 @@ __global__ void __launch_bounds__(kBrNT, 1) bwd_res_kernel(BwdResArgs a) {
     int own[PX];  // (ly << 16) | lx, or -1 outside the image / part
     const rsrc_t ra = make_rsrc(a.aff + b * (K + 1) * HW);
     const rsrc_t ro = make_rsrc(a.off + b * a.off_bs);
-    const unsigned plane_bytes = (unsigned)HW * 4u;
+    constexpr unsigned ES = sizeof(S);
+    const unsigned plane_bytes = (unsigned)HW * ES;
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
         const int i = tid + j * NT;
@@ -145,17 +151,17 @@ __global__ void __launch_bounds__(kBrNT, 1) bwd_res_kernel(BwdResArgs a) {
         const int y = y0 + ly, x = x0 + lx;
         const bool act = i < PR * PC && y < H && x < W;
         own[j] = act ? (ly << 16) | lx : -1;
-        const unsigned vpix = (act ? (unsigned)(y * W + x) : 0u) * 4u;
+        const unsigned vpix = (act ? (unsigned)(y * W + x) : 0u) * ES;
         float asum = 0.f;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            const float v = bld(ra, vpix, (unsigned)(k < REF ? k : k + 1) * plane_bytes);
+            const float v = blds<S>(ra, vpix, (unsigned)(k < REF ? k : k + 1) * plane_bytes);
             if (i < npx) avl[i * K + k] = v;
             asum += v;
             const int t = k < REF ? k : k + 1;
             const int ti = t / 3, tj = t % 3;
-            hs[j][k] = (float)(y - 1 + ti) + bld(ro, vpix, (2u * k) * plane_bytes);
-            ws[j][k] = (float)(x - 1 + tj) + bld(ro, vpix, (2u * k + 1) * plane_bytes);
+            hs[j][k] = (float)(y - 1 + ti) + blds<S>(ro, vpix, (2u * k) * plane_bytes);
+            ws[j][k] = (float)(x - 1 + tj) + blds<S>(ro, vpix, (2u * k + 1) * plane_bytes);
         }
         // aref = 1 - sum a_k; the scatter bound |aref| + sum |a_k| (bwd_step_kernel's order)
         aref[j] = 1.0f - asum;
@@ -165,8 +171,8 @@ __global__ void __launch_bounds__(kBrNT, 1) bwd_res_kernel(BwdResArgs a) {
             for (int k = 0; k < K; ++k) m += fabsf(avl[(i < npx ? i : 0) * K + k]);
             amass[j] = m;
         }
-        ce[j] = has_conf ? bld(make_rsrc(a.conf_eff + b * HW), vpix, 0u) : 1.f;
-        const float dv = preserve ? bld(make_rsrc(a.dep + b * HW), vpix, 0u) : 0.f;
+        ce[j] = has_conf ? blds<S>(make_rsrc(a.conf_eff + b * HW), vpix, 0u) : 1.f;
+        const float dv = preserve ? blds<S>(make_rsrc(a.dep + b * HW), vpix, 0u) : 0.f;
         pm[j] = 1.0f - (dv > 0.f ? 1.f : 0.f);
         gcv[j] = 0.f;
     }
@@ -238,11 +244,11 @@ __global__ void __launch_bounds__(kBrNT, 1) bwd_res_kernel(BwdResArgs a) {
             if (ctl[0]) { t_abort = t; break; }
         }
         // ---- 2./3. dL/df_t at the own pixels, dL/dout_t
-        const float *pt_p = a.pred_inter + (size_t)(t - 1) * a.N + b * HW;
-        const float *gi_p = a.g_inter ? a.g_inter + (size_t)(t - 1) * a.N + b * HW : nullptr;
+        const S *pt_p = a.pred_inter + (size_t)(t - 1) * a.N + b * HW;
+        const S *gi_p = a.g_inter ? a.g_inter + (size_t)(t - 1) * a.N + b * HW : nullptr;
         const int jgo = t - 1;
-        float *go_p = jgo < 2 * K ? a.g_off + b * a.goff_bs + (size_t)jgo * HW
-                                  : a.g_aff + b * a.gaff_bs + (size_t)(jgo - 2 * K) * HW;
+        float *go_p = jgo < a.go_na ? a.go_a + b * a.go_a_bs + (size_t)jgo * HW
+                                    : a.go_b + b * a.go_b_bs + (size_t)(jgo - a.go_na) * HW;
         float *gfr_p = gfb[t & 1];
         float go[PX], mass = 0.f;
 #pragma unroll
@@ -258,10 +264,10 @@ __global__ void __launch_bounds__(kBrNT, 1) bwd_res_kernel(BwdResArgs a) {
                                      : __hip_atomic_exchange(&gfr_p[cell], 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 gfr = (mine + others) + refc[j];
             }
-            const float pt = pt_p[cell];
+            const float pt = ld<S>(pt_p + cell);
             float g = has_conf ? gfr * ce[j] : gfr;
-            if (gi_p) g += gi_p[cell];
-            if (last && a.g_pred) g += pt >= 0.f ? a.g_pred[b * HW + cell] : 0.f;  // pred = clamp(p_T, 0)
+            if (gi_p) g += ld<S>(gi_p + cell);
+            if (last && a.g_pred) g += pt >= 0.f ? ld<S>(a.g_pred + b * HW + cell) : 0.f;  // pred = clamp(p_T, 0)
             if (has_conf) gcv[j] = gcv[j] + gfr * pt;
             go[j] = preserve ? pm[j] * g : g;
             go_p[cell] = go[j];
@@ -380,8 +386,8 @@ __global__ void __launch_bounds__(kBrNT, 1) bwd_res_kernel(BwdResArgs a) {
         if (t_abort) __hip_atomic_store(&gfb[0][cell], __builtin_nanf(""), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         for (int t = t_abort; t >= 1; --t) {
             const int jgo = t - 1;
-            float *go_p = jgo < 2 * K ? a.g_off + b * a.goff_bs + (size_t)jgo * HW
-                                      : a.g_aff + b * a.gaff_bs + (size_t)(jgo - 2 * K) * HW;
+            float *go_p = jgo < a.go_na ? a.go_a + b * a.go_a_bs + (size_t)jgo * HW
+                                        : a.go_b + b * a.go_b_bs + (size_t)(jgo - a.go_na) * HW;
             go_p[cell] = __builtin_nanf("");
         }
     }

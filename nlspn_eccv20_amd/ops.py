@@ -27,7 +27,7 @@ differentiable wherever ModulatedDeformConvFunction appears
 torch.compile traces a training step through them:
 
   torch.ops.nlspn.propagate_backward             nlspn_propagate_backward (the section)
-  torch.ops.nlspn.prop_step_backward             nlspn_prop_step_backward (raw offsets, float32)
+  torch.ops.nlspn.prop_step_backward             nlspn_prop_step_backward (raw offsets)
   torch.ops.nlspn.affinity_normalization_backward  nlspn_affinity_normalize_backward
   torch.ops.nlspn.modulated_deform_conv_backward  (the seam-2 op above)
 
@@ -167,7 +167,7 @@ def _register_autograd() -> None:
 
     @affinity_normalization_backward.register_fake
     def _(aff, gamma, g_out, kind):
-        return torch.empty_like(aff, dtype=torch.float32), torch.empty_like(gamma)
+        return torch.empty_like(aff), torch.empty_like(gamma)  # aff's dtype (float32 or float16)
 
     # ---- autograd of the forward ops
     def setup_propagate(ctx, inputs, output):

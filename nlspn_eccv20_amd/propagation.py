@@ -13,11 +13,13 @@ per-batch strides are passed through, so the (B, 3K, H, W) head output can be
 sliced into offsets/affinities without a copy (nlspnmodel.py:304-305).
 Computation is fp32; storage may be fp32 or fp16.
 
-propagate() is differentiable (float32 storage): its backward is the native
+propagate() is differentiable in both storage types: its backward is the native
 nlspn_propagate_backward (DCN col2im/col2im_coord + the autograd of the blends,
 clamps and affinity normalisation), giving gradients for pred_init, confidence,
-the raw affinity, the raw offsets and gamma.  prop_step() and
-affinity_normalization() are inference building blocks.
+the raw affinity, the raw offsets and gamma.  With float16 storage the gradients
+(gamma's apart) are float16, each the float32 value rounded once; nothing is
+accumulated in half.  prop_step() and affinity_normalization() are differentiable
+the same way.
 """
 from __future__ import annotations
 
@@ -130,16 +132,16 @@ class _AffNormFn(torch.autograd.Function):
 def _affnorm_backward(aff, gamma, g_out, kind, want_gamma=True):
     """nlspn_affinity_normalize_backward: gradients of the (K+1)-tap normalised affinity
     with respect to the raw taps and (TGASS, want_gamma) gamma (else None)."""
-    if aff.dtype != torch.float32:
-        raise NotImplementedError("the affinity-normalisation backward is implemented for float32 storage")
     B, K, H, W = aff.shape
     f32 = dict(dtype=torch.float32, device=aff.device)
     g_out = g_out.contiguous()
-    g_raw = torch.empty((B, K, H, W), **f32)
+    if g_out.dtype != aff.dtype:
+        raise RuntimeError("the incoming gradient must have aff's dtype")
+    g_raw = torch.empty((B, K, H, W), dtype=aff.dtype, device=aff.device)
     want_g = kind == "TGASS" and want_gamma
     g_gamma = torch.empty(1, **f32) if want_g else None
     ws = torch.empty(max(1, _lib.get().nlspn_affinity_normalize_backward_workspace_bytes(B, K, H, W) // 4), **f32)
-    _lib.call("nlspn_affinity_normalize_backward", aff.device, _lib.DTYPE_F32, aff, _planes("aff", aff, B, K, H, W),
+    _lib.call("nlspn_affinity_normalize_backward", aff.device, _dtype_code(aff), aff, _planes("aff", aff, B, K, H, W),
               _gamma_f32(gamma), g_out, g_raw, g_gamma, ws, B, K, H, W, _lib.AFF_KINDS[kind], STREAM)
     if g_gamma is not None:
         g_gamma = g_gamma.reshape(gamma.shape).to(gamma.dtype)
@@ -149,7 +151,7 @@ def _affnorm_backward(aff, gamma, g_out, kind, want_gamma=True):
 def affinity_normalization(aff: torch.Tensor, gamma: torch.Tensor, kind: str = "TGASS") -> torch.Tensor:
     """NLSPNModel._affinity_normalization + _aff_insert (nlspnmodel.py:179-201, :261-269).
     aff (B, K, H, W) raw -> (B, K+1, H, W), reference tap at K//2.  Differentiable
-    (float32) in aff and, for TGASS, gamma."""
+    in aff and, for TGASS, gamma (float16 storage: float16 gradient for aff)."""
     if torch.is_grad_enabled() and (aff.requires_grad or (torch.is_tensor(gamma) and gamma.requires_grad)):
         return _AffNormFn.apply(aff, gamma, kind)
     top = _torch_ops()
@@ -194,8 +196,8 @@ def _prop_step(feat, confidence, dep, aff, offset, kernel, offset_layout, preser
 
 
 class _PropStepFn(torch.autograd.Function):
-    """Autograd node for one prop_step; backward = nlspn_prop_step_backward (float32,
-    raw offset layout).  dep receives no gradient (the reference's sparse input)."""
+    """Autograd node for one prop_step; backward = nlspn_prop_step_backward (raw offset
+    layout; gradients in the storage dtype).  dep receives no gradient (the reference's sparse input)."""
 
     @staticmethod
     def forward(ctx, feat, confidence, dep, aff, offset, kernel, offset_layout, preserve_input, always_clip):
@@ -218,20 +220,23 @@ def _step_backward(feat, conf, dep, aff, off, g_out, kh, kw, preserve, clip):
     """nlspn_prop_step_backward: gradients of one iteration with respect to feat,
     confidence, the normalised (K+1)-tap affinity (tap K/2 zero: recomputed in-kernel as
     1 - sum) and the raw offsets (None where the input is absent)."""
-    if feat.dtype != torch.float32:
-        raise NotImplementedError("the prop_step backward is implemented for float32 storage")
     B, _, H, W = feat.shape
     K = kh * kw - 1
-    f32 = dict(dtype=torch.float32, device=feat.device)
-    g_feat = torch.empty((B, 1, H, W), **f32)
-    g_conf = torch.empty((B, 1, H, W), **f32) if conf is not None else None
-    g_aff = torch.empty((B, K + 1, H, W), **f32)
-    g_off = torch.empty((B, 2 * K, H, W), **f32) if off is not None else None
-    ws = torch.empty(_lib.get().nlspn_prop_step_backward_workspace_bytes(B, H, W) // 4, **f32)
+    dt = _dtype_code(feat)
+    g_out = g_out.contiguous()
+    if g_out.dtype != feat.dtype or aff.dtype != feat.dtype or (off is not None and off.dtype != feat.dtype):
+        raise RuntimeError("aff, offset and the incoming gradient must have feat's dtype")
+    st = dict(dtype=feat.dtype, device=feat.device)  # gradients in the storage dtype
+    g_feat = torch.empty((B, 1, H, W), **st)
+    g_conf = torch.empty((B, 1, H, W), **st) if conf is not None else None
+    g_aff = torch.empty((B, K + 1, H, W), **st)
+    g_off = torch.empty((B, 2 * K, H, W), **st) if off is not None else None
+    ws = torch.empty(_lib.get().nlspn_prop_step_backward_workspace_bytes_dtype(dt, B, H, W, kh, kw) // 4,
+                     dtype=torch.float32, device=feat.device)
     abs_ = _planes("aff", aff, B, K + 1, H, W)
     obs = _planes("offset", off, B, 2 * K, H, W) if off is not None else 0
-    _lib.call("nlspn_prop_step_backward", feat.device, _lib.DTYPE_F32, feat, conf, dep, aff, abs_, off, obs,
-              g_out.contiguous(), g_feat, g_conf, g_aff, g_off, ws, B, H, W, kh, kw, _lib.flags(preserve, clip), STREAM)
+    _lib.call("nlspn_prop_step_backward", feat.device, dt, feat, conf, dep, aff, abs_, off, obs,
+              g_out, g_feat, g_conf, g_aff, g_off, ws, B, H, W, kh, kw, _lib.flags(preserve, clip), STREAM)
     return g_feat, g_conf, g_aff, g_off
 
 
@@ -245,7 +250,7 @@ def prop_step(feat: torch.Tensor, confidence: Optional[torch.Tensor], dep: Optio
     aff: normalised (B, K+1, H, W) (the output of affinity_normalization; its tap K//2 is
     recomputed in-kernel as 1 - sum of the others).  offset: (B, 2(K+1), H, W) inserted
     layout or (B, 2K, H, W) with offset_layout="raw"; None = no-offset branch (3x3 replicate).
-    Differentiable (float32, raw offsets) in feat, confidence, aff and offset when called
+    Differentiable (raw offsets; gradients in the storage dtype) in feat, confidence, aff and offset when called
     without out/pred_out.
     """
     if (out is None and pred_out is None and torch.is_grad_enabled()
@@ -353,29 +358,32 @@ def _section_backward(pred_init, dep, conf, aff, off, gamma, pred_inter, aff_nor
     to pred_init, confidence, the raw affinity, the raw offsets and gamma (None where the
     input is absent; g_gamma None unless TGASS).  packed: the affinity and offset
     gradients as slices of one (B, 3K, H, W) buffer, returned last (else None)."""
-    if pred_init.dtype != torch.float32:
-        raise NotImplementedError("the propagation backward is implemented for float32 storage")
     B, _, H, W = pred_init.shape
     K = kh * kw - 1
     dev = pred_init.device
+    dt = _dtype_code(pred_init)
     f32 = dict(dtype=torch.float32, device=dev)
+    st = dict(dtype=pred_init.dtype, device=dev)  # gradients in the storage dtype (gamma's stays float32)
     g_pred = None if g_pred is None else g_pred.contiguous()
     g_inter = None if g_inter is None else g_inter.contiguous()
-    g_pi = torch.empty((B, 1, H, W), **f32)
-    g_conf = torch.empty((B, 1, H, W), **f32) if conf is not None else None
+    for t in (g_pred, g_inter, pred_inter, aff_norm, conf_eff):
+        if t is not None and t.dtype != pred_init.dtype:
+            raise RuntimeError("the saved tensors and incoming gradients must have pred_init's dtype")
+    g_pi = torch.empty((B, 1, H, W), **st)
+    g_conf = torch.empty((B, 1, H, W), **st) if conf is not None else None
     g_oa = None
     if packed:  # one (B, 3K, H, W) gradient: offsets in planes 0..2K-1, affinity after
-        g_oa = torch.empty((B, 3 * K, H, W), **f32)
+        g_oa = torch.empty((B, 3 * K, H, W), **st)
         g_off, g_aff, gbs = g_oa[:, :2 * K], g_oa[:, 2 * K:], 3 * K * H * W
     else:
-        g_aff = torch.empty((B, K, H, W), **f32)
-        g_off = torch.empty((B, 2 * K, H, W), **f32) if off is not None else None
+        g_aff = torch.empty((B, K, H, W), **st)
+        g_off = torch.empty((B, 2 * K, H, W), **st) if off is not None else None
         gbs = 0
     g_gamma = torch.zeros(1, **f32)
-    ws = torch.empty(_lib.get().nlspn_backward_workspace_bytes(B, H, W, kh, kw) // 4, **f32)
+    ws = torch.empty(_lib.get().nlspn_backward_workspace_bytes_dtype(dt, B, H, W, kh, kw, T) // 4, **f32)
     abs_ = _planes("aff", aff, B, K, H, W)
     obs = _planes("offset", off, B, 2 * K, H, W) if off is not None else 0
-    _lib.call("nlspn_propagate_backward", dev, _lib.DTYPE_F32, pred_init, dep, conf, aff, abs_, off, obs,
+    _lib.call("nlspn_propagate_backward", dev, dt, pred_init, dep, conf, aff, abs_, off, obs,
               _gamma_f32(gamma), pred_inter, aff_norm, conf_eff, g_pred, g_inter, g_pi, g_conf, g_aff, gbs, g_off, gbs,
               g_gamma, ws, B, H, W, kh, kw, T, _lib.AFF_KINDS[affinity], _lib.flags(preserve, clip), STREAM)
     g_gamma = g_gamma.reshape(gamma.shape).to(gamma.dtype) if affinity == "TGASS" else None
@@ -393,7 +401,8 @@ def _packed_head(aff, offset):
     if offset is None or aff._base is None or offset._base is not aff._base:
         return None
     base = aff._base
-    if not base.requires_grad or base.dim() != 4 or not base.is_contiguous() or base.dtype != torch.float32:
+    if (not base.requires_grad or base.dim() != 4 or not base.is_contiguous()
+            or base.dtype not in (torch.float32, torch.float16)):
         return None
     # slices taken under no_grad report requires_grad but have no grad_fn: not in the graph
     if not (aff.requires_grad and offset.requires_grad) or aff.grad_fn is None or offset.grad_fn is None:

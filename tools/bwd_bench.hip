@@ -39,7 +39,7 @@ struct Variant {
 
 template <int TH, int TW, int R, int DIAG, bool SPLIT = false>
 Variant mk(const char *name) {
-    return Variant{name, reinterpret_cast<const void *>(&bwd_step_kernel<3, 3, TH, TW, R, R, 4, true, false, DIAG, SPLIT>),
+    return Variant{name, reinterpret_cast<const void *>(&bwd_step_kernel<float, 3, 3, TH, TW, R, R, 4, true, false, DIAG, SPLIT>),
                    TH, TW};
 }
 
